@@ -1,13 +1,20 @@
 """PinSAGE train-step throughput on MI355X (BASELINE.json metric).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c3|c4] [--scaling weak|strong]
-                    [--no-cpu-baseline]
+                    [--dump-outputs DIR] [--full [--no-cpu-baseline]]
 
 A step = sample_batch (reference RNG semantics, host) + PinSage.train_batch
 (fused HIP forward of the query/positive/negative ids, loss, backward, Adam)
 on a synthetic playlist graph resident in HBM.  N > 1: one process per GPU
 (torch.distributed over RCCL), each rank trains batch_size triples per step
 (weak scaling), gradients all-reduced.  Prints ONE JSON line on rank 0.
+
+A plain run sets up, warms up, times the K steps and prints the headline line
+(metric, value, ms_per_step, the config).  --dump-outputs DIR then writes what
+the last timed step handed its caller (DIR/<name>.npy, see dump_outputs).
+--full adds everything that takes runs of its own: the warm precompute
+timing, the per-kernel timing pass with the roofline / gather / frontier
+figures, and the CPU baseline (--no-cpu-baseline leaves that one out).
 """
 from __future__ import annotations
 
@@ -310,7 +317,13 @@ def main():
     ap.add_argument("--steps", type=int, default=None, help="default 50 (c5: 3)")
     ap.add_argument("--warmup", type=int, default=None, help="default 5 (c5: 1)")
     ap.add_argument("--config", default="c2", choices=sorted(CONFIGS))
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baseline out")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the warm precompute timing, the "
+                         "per-kernel timing pass (roofline, gather kernel, frontier sizes) and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one returned and the parameters it left "
+                         "as DIR/<name>.npy")
     ap.add_argument("--scale", type=float, default=1.0,
                     help="rehearsal only: scale the graph (tracks, collections, memberships)")
     ap.add_argument("--precompute-rng", default="philox", choices=["philox", "mt19937"])
@@ -321,6 +334,12 @@ def main():
                          "fly: every call walks its nodes' neighbourhoods inside the step "
                          "(relevant_nodes_per_layer, pinsage_model.py:142-154), RNG per --precompute-rng")
     args = ap.parse_args()
+    if args.steps is not None and args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.warmup is not None and args.warmup < 0:
+        ap.error("--warmup must not be negative")
+    if args.dump_outputs is not None:  # (the steps run from a temporary directory)
+        args.dump_outputs = os.path.abspath(args.dump_outputs)
     launch_ranks(args.gpus)
     cfg = dict(CONFIGS[args.config])
     if args.scale != 1.0:
@@ -347,7 +366,7 @@ def main():
     hops = cfg["n_tracks"] * 500
     log(f"[bench] precompute ({args.precompute_rng}) {t_pre:.2f}s = {hops/t_pre/1e6:.1f} M hops/s")
     t_pre_warm = None
-    if t_pre < 2.0 and not micro:  # the first call pays one-time costs (code objects, CSR upload): time it again
+    if args.full and t_pre < 2.0 and not micro:  # the first call pays one-time costs (code objects, CSR upload): time it again
         _, t_pre_warm = precompute(g, cfg, args.precompute_rng)
         log(f"[bench] precompute again (warm) {t_pre_warm * 1e3:.1f} ms")
 
@@ -399,7 +418,7 @@ def main():
             ta = time.perf_counter()
             batch, _ = tr.next_batch()
             tb = time.perf_counter()
-            loss = tr.train_batch(batch)[0]
+            last = tr.train_batch(batch)
             t_sample += tb - ta
             t_enqueue += time.perf_counter() - tb
         t_wait = (fz.ring_wait_s() - w0) if fz is not None else 0.0
@@ -421,37 +440,131 @@ def main():
         value = 3 * cfg["batch"] * world * args.steps / elapsed
 
         gemm_choices = tr._fused.tuned_choices if tr._fused is not None else None
-        # per-kernel timing pass (HIP events on the launch stream), separate from the timed
-        # loop; runs the same kernels eagerly (events are not recorded inside the graph)
-        fused_any = tr._fused if tr._fused is not None else getattr(tr, "_fused_fly", None)
-        if fused_any is not None:
-            fused_any.use_graph = False
-        eng = tr.model.runner().engine
-        nat.lib().pinsage_engine_timing(eng.h, 1)
-        n_t = 1 if micro else max(5, min(20, args.steps))
-        sizes = []
-        hold_stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-        for _ in range(n_t):
-            # hold the stream while the host queues the step, so the events time the
-            # kernels back to back (an eager step's host enqueue is ~0.5 ms: without
-            # the hold, an idle GPU would charge each launch's host gap to its kernel)
-            if not micro:
-                nat.lib().pinsage_stream_hold(3000, hold_stream)
-            step()
-            torch.cuda.synchronize()
-            off = eng.off
-            # micro-batched: the frontier of the last slice's outputs-only forward
-            rn = tr.model.runner()
-            ws = fused_any.ws if fused_any is not None else (rn._ws if rn._ws is not None else rn.last_ws)
-            cN0 = int(eng.view(ws, int(off.count_N[0]), torch.int32, 1).item())
-            cS0 = int(eng.view(ws, int(off.count_S[0]), torch.int32, 1).item())
-            cN1 = (int(eng.view(ws, int(off.count_N[1]), torch.int32, 1).item())
-                   if cfg["n_layers"] > 1 else 0)
-            sizes.append((cN0, cS0, cN1))
-        kt = kernel_table(eng)
-        nat.lib().pinsage_engine_timing(eng.h, 0)
+        if args.dump_outputs is not None and rank == 0:
+            dump_outputs(args.dump_outputs, last, tr.model)
+        if args.full:
+            # per-kernel timing pass (HIP events on the launch stream), separate from the timed
+            # loop; runs the same kernels eagerly (events are not recorded inside the graph)
+            fused_any = tr._fused if tr._fused is not None else getattr(tr, "_fused_fly", None)
+            if fused_any is not None:
+                fused_any.use_graph = False
+            eng = tr.model.runner().engine
+            nat.lib().pinsage_engine_timing(eng.h, 1)
+            n_t = 1 if micro else max(5, min(20, args.steps))
+            sizes = []
+            hold_stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+            for _ in range(n_t):
+                # hold the stream while the host queues the step, so the events time the
+                # kernels back to back (an eager step's host enqueue is ~0.5 ms: without
+                # the hold, an idle GPU would charge each launch's host gap to its kernel)
+                if not micro:
+                    nat.lib().pinsage_stream_hold(3000, hold_stream)
+                step()
+                torch.cuda.synchronize()
+                off = eng.off
+                # micro-batched: the frontier of the last slice's outputs-only forward
+                rn = tr.model.runner()
+                ws = fused_any.ws if fused_any is not None else (rn._ws if rn._ws is not None else rn.last_ws)
+                cN0 = int(eng.view(ws, int(off.count_N[0]), torch.int32, 1).item())
+                cS0 = int(eng.view(ws, int(off.count_S[0]), torch.int32, 1).item())
+                cN1 = (int(eng.view(ws, int(off.count_N[1]), torch.int32, 1).item())
+                       if cfg["n_layers"] > 1 else 0)
+                sizes.append((cN0, cS0, cN1))
+            kt = kernel_table(eng)
+            nat.lib().pinsage_engine_timing(eng.h, 0)
         os.chdir(cwd)
 
+    result = {
+        "metric": "PinSAGE train-step nodes/sec (2-hop, batch 512) at 1/2/4/8 MI355X",
+        "value": value,
+        "unit": "target nodes/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": ms_per_step,
+        "higher_is_better": True,
+        "scaling": args.scaling,
+        "vs_baseline": None,
+        "dtype": "f32",
+        "data": "synthetic (seeded playlist graph, N(0,1) features, co-membership positives)",
+        "config": {"workload": cfg["workload"], "n_tracks": cfg["n_tracks"], "n_cols": cfg["n_cols"],
+                   "memberships": cfg["memberships"], "d_in": cfg["d_in"], "hidden": 512, "out": 128,
+                   "n_layers": cfg["n_layers"], "fanout": cfg["T"], "batch_per_gpu": cfg["batch"],
+                   "global_batch": cfg["batch"] * world, "parallelism": f"dp{world}",
+                   "batch_rng": "mt19937 (reference-exact)", "sampling": args.sampling},
+        "full": args.full,
+        "host_ms_per_step": {"sample_batch": t_sample / args.steps * 1e3,
+                             "train_batch_enqueue": t_enqueue / args.steps * 1e3,
+                             # the enqueue's own host work: without the time blocked on
+                             # ring slots while the device is behind
+                             "train_batch_enqueue_excl_ring_wait": (t_enqueue - t_wait) / args.steps * 1e3,
+                             "native_step": native_step,
+                             # inside the native step call (pinsage_stepper_stats): all of
+                             # it, and the graph launches alone
+                             **({"native_call": (st_stats["call_ns"] - st0["call_ns"]) / args.steps * 1e-6,
+                                 "graph_launch": (st_stats["launch_ns"] - st0["launch_ns"]) / args.steps * 1e-6}
+                                if st_stats is not None and st0 is not None else {})},
+        "precompute": {"seconds": t_pre, "seconds_warm": t_pre_warm, "rng": args.precompute_rng,
+                       "hops_per_s": hops / t_pre,
+                       "hops_per_s_warm": hops / t_pre_warm if t_pre_warm else None,
+                       "note": "wall time of precompute_neighborhoods_topt incl. the [n,100] f64+i64 "
+                               "table's device-to-host copy; sampler kernels alone: "
+                               "tools/precompute_probe.py"},
+        "gemm_choices": gemm_choices,
+    }
+    if micro:
+        result["config"]["micro_batch"] = micro
+    if cfg.get("device_build"):
+        result["data"] += "; graph, features and positives drawn on the device"
+        result["precompute"]["note"] = ("precompute_device_table: the model's T=50 columns of the top-100, "
+                                        "built and kept in HBM")
+    if args.dump_outputs is not None:
+        result["dump_outputs"] = args.dump_outputs
+    if args.full:
+        result.update(kernel_report(args, cfg, kt, sizes, nat.lib().pinsage_gemm_get_prec()))
+        result["cpu_baseline"] = None
+        if rank == 0 and world == 1 and micro:
+            # the reference's put_embeddings clones (n x d_in x 4 = 82 GB each)
+            # and its dense [256, N_all] f64 visit matrix (205 GB) exceed the host: not run
+            result["cpu_baseline"] = {"value": None, "note": "not run: the reference's per-layer put_embeddings "
+                                      "clones (82 GB each) and dense visit matrices do not fit host memory"}
+        elif rank == 0 and world == 1 and not args.no_cpu_baseline:
+            try:
+                result["cpu_baseline"] = cpu_baseline(cfg, pg, feats, pos, nbhds)
+            except Exception as ex:  # report, never fail the bench line
+                result["cpu_baseline"] = {"error": repr(ex)}
+    if rank == 0:
+        print(json.dumps(result), flush=True)
+    if world > 1:
+        torch.distributed.destroy_process_group()
+
+
+def dump_outputs(out_dir, last, model, budget=64 << 20):
+    """What the last timed step handed its caller, as out_dir/<name>.npy (float32):
+    train_batch's return values (loss, node_feat_loss, variance; a path that
+    returns None for one writes no file for it) and the parameters its Adam
+    update left in the model (param.<name>).  At most `budget` bytes in all: an
+    array over its share is cut to a fixed, seeded sample of its elements.
+    The caller has synchronized the device."""
+    arrays = {}
+    for name, v in zip(("loss", "node_feat_loss", "variance"), last):
+        if v is not None:
+            arrays[name] = torch.as_tensor(v).detach().float().cpu().numpy().reshape(-1)
+    for name, p in model.named_parameters():
+        arrays["param." + name] = p.detach().float().cpu().numpy()
+    share = budget // max(1, len(arrays)) // 4
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        if a.size > share:
+            pick = np.sort(np.random.default_rng(0).choice(a.size, size=share, replace=False))
+            a = a.reshape(-1)[pick]
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
+
+
+def kernel_report(args, cfg, kt, sizes, prec):
+    """The --full figures of the per-kernel timing pass: kt = kernel_table of the
+    eager steps, sizes = their (U0, F0, U1) frontier counts, prec = the GEMM
+    precision mode (pinsage_gemm_get_prec)."""
     U0 = float(np.mean([s[0] for s in sizes]))
     F0 = float(np.mean([s[1] for s in sizes]))
     U1 = float(np.mean([s[2] for s in sizes]))
@@ -494,7 +607,6 @@ def main():
     a_traffic, a_traffic_src, _ = pmc_traffic(pmc_key, a_site)
     kernels = {k: {"avg_ms": v[0] / max(v[1], 1), "calls": v[1]} for k, v in sorted(kt.items())}
     traffic, traffic_src, mfma_busy = pmc_traffic(pmc_key, "fwd.q_gemm.l0")
-    prec = nat.lib().pinsage_gemm_get_prec()
     gemm_arith = ("split bf16: each fp32 operand = hi + mid + lo bf16 (exact to 2^-26), six "
                   "v_mfma_f32_32x32x16_bf16 products per 16-k step, fp32 accumulation; achieved/peak are "
                   "algorithmic fp32 FLOP against the fp32 MFMA peak, executed bf16 MFMA work is 6x "
@@ -527,24 +639,7 @@ def main():
               "algorithmic_bytes_per_launch": 4.0 * (U0 * hid + U0 * d + 7 * d * hid + 4 * hid)}
     # `roofline` is the dominant (longest) of the two launches; the other beside it
     roof, roof_other = (w_roof, q_roof) if w_avg > q_avg else (q_roof, w_roof)
-    result = {
-        "metric": "PinSAGE train-step nodes/sec (2-hop, batch 512) at 1/2/4/8 MI355X",
-        "value": value,
-        "unit": "target nodes/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": ms_per_step,
-        "higher_is_better": True,
-        "scaling": args.scaling,
-        "vs_baseline": None,
-        "dtype": "f32",
-        "data": "synthetic (seeded playlist graph, N(0,1) features, co-membership positives)",
-        "config": {"workload": cfg["workload"], "n_tracks": cfg["n_tracks"], "n_cols": cfg["n_cols"],
-                   "memberships": cfg["memberships"], "d_in": cfg["d_in"], "hidden": hid, "out": 128,
-                   "n_layers": cfg["n_layers"], "fanout": T, "batch_per_gpu": cfg["batch"],
-                   "global_batch": cfg["batch"] * world, "parallelism": f"dp{world}",
-                   "batch_rng": "mt19937 (reference-exact)", "sampling": args.sampling},
+    report = {
         "roofline": roof,
         "roofline_other": roof_other,
         "gather_kernel": {"kernel": a_site + (" (weighted aggregation + [h_self || agg] W projection, "
@@ -578,48 +673,11 @@ def main():
                                   + "; logical counts every (row, slot) read, most served by L2 / "
                                     "Infinity Cache"},
         "frontier": {"U0_mean": U0, "F0_mean": F0, "U1_mean": U1},
-        "host_ms_per_step": {"sample_batch": t_sample / args.steps * 1e3,
-                             "train_batch_enqueue": t_enqueue / args.steps * 1e3,
-                             # the enqueue's own host work: without the time blocked on
-                             # ring slots while the device is behind
-                             "train_batch_enqueue_excl_ring_wait": (t_enqueue - t_wait) / args.steps * 1e3,
-                             "native_step": native_step,
-                             # inside the native step call (pinsage_stepper_stats): all of
-                             # it, and the graph launches alone
-                             **({"native_call": (st_stats["call_ns"] - st0["call_ns"]) / args.steps * 1e-6,
-                                 "graph_launch": (st_stats["launch_ns"] - st0["launch_ns"]) / args.steps * 1e-6}
-                                if st_stats is not None and st0 is not None else {})},
-        "precompute": {"seconds": t_pre, "seconds_warm": t_pre_warm, "rng": args.precompute_rng,
-                       "hops_per_s": hops / t_pre,
-                       "hops_per_s_warm": hops / t_pre_warm if t_pre_warm else None,
-                       "note": "wall time of precompute_neighborhoods_topt incl. the [n,100] f64+i64 "
-                               "table's device-to-host copy; sampler kernels alone: "
-                               "tools/precompute_probe.py"},
-        "gemm_choices": gemm_choices,
         "kernels": kernels,
-        "cpu_baseline": None,
     }
-    if micro:
-        result["config"]["micro_batch"] = micro
-        result["frontier"]["note"] = "U0/F0 of one micro-batch slice (the last outputs-only forward)"
-    if cfg.get("device_build"):
-        result["data"] += "; graph, features and positives drawn on the device"
-        result["precompute"]["note"] = ("precompute_device_table: the model's T=50 columns of the top-100, "
-                                        "built and kept in HBM")
-    if rank == 0 and world == 1 and micro:
-        # the reference's put_embeddings clones (n x d_in x 4 = 82 GB each)
-        # and its dense [256, N_all] f64 visit matrix (205 GB) exceed the host: not run
-        result["cpu_baseline"] = {"value": None, "note": "not run: the reference's per-layer put_embeddings "
-                                  "clones (82 GB each) and dense visit matrices do not fit host memory"}
-    elif rank == 0 and world == 1 and not args.no_cpu_baseline:
-        try:
-            result["cpu_baseline"] = cpu_baseline(cfg, pg, feats, pos, nbhds)
-        except Exception as ex:  # report, never fail the bench line
-            result["cpu_baseline"] = {"error": repr(ex)}
-    if rank == 0:
-        print(json.dumps(result), flush=True)
-    if world > 1:
-        torch.distributed.destroy_process_group()
+    if cfg.get("micro_batch"):
+        report["frontier"]["note"] = "U0/F0 of one micro-batch slice (the last outputs-only forward)"
+    return report
 
 
 if __name__ == "__main__":

@@ -393,3 +393,32 @@ def test_bench_refuses_a_world_size_other_than_gpus():
     r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "2"], cwd=REPO, env=env,
                        capture_output=True, text=True, timeout=120)
     assert r.returncode != 0 and "WORLD_SIZE=3" in (r.stderr + r.stdout)
+
+
+def test_bench_dump_outputs_writes_float32_within_its_budget(tmp_path):
+    """bench.dump_outputs (--dump-outputs DIR): one float32 DIR/<name>.npy per
+    value train_batch returned (none for a None) and per model parameter; an
+    array over its share of the byte budget becomes a sample of its elements
+    that is the same on every run."""
+    import torch
+    import bench
+    torch.manual_seed(3)
+    model = torch.nn.Sequential(torch.nn.Linear(7, 5), torch.nn.Linear(5, 3, bias=False))
+    last = (torch.tensor(0.25), None, torch.tensor(1.5, dtype=torch.float64))
+    bench.dump_outputs(str(tmp_path / "a"), last, model)
+    got = {p.name: np.load(p) for p in (tmp_path / "a").iterdir()}
+    assert sorted(got) == ["loss.npy", "param.0.bias.npy", "param.0.weight.npy", "param.1.weight.npy",
+                           "variance.npy"]
+    assert all(a.dtype == np.float32 for a in got.values())
+    assert got["loss.npy"].tolist() == [0.25] and got["variance.npy"].tolist() == [1.5]
+    assert np.array_equal(got["param.0.weight.npy"], model[0].weight.detach().numpy())
+    # 5 arrays share 200 bytes: 10 floats each, so only the 7x5 and 5x3 weights are sampled
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), last, model, budget=200)
+    small = {p.name: np.load(p) for p in (tmp_path / "b").iterdir()}
+    again = {p.name: np.load(p) for p in (tmp_path / "c").iterdir()}
+    assert sum(a.nbytes for a in small.values()) <= 200
+    assert small["param.0.weight.npy"].shape == (10,) and small["param.1.weight.npy"].shape == (10,)
+    assert np.isin(small["param.0.weight.npy"], got["param.0.weight.npy"]).all()
+    assert np.array_equal(small["param.0.bias.npy"], got["param.0.bias.npy"])
+    assert sorted(small) == sorted(again) and all(np.array_equal(small[k], again[k]) for k in small)

@@ -6,6 +6,6 @@ mkdir -p $out
 i=0
 for v in $vals; do
   i=$((i+1))
-  env $var=$v timeout -k 10 200 python bench.py --no-cpu-baseline "$@" > $out/${i}_$v.json 2>$out/${i}_$v.err || { tail $out/${i}_$v.err; exit 1; }
+  env $var=$v timeout -k 10 200 python bench.py --full --no-cpu-baseline "$@" > $out/${i}_$v.json 2>$out/${i}_$v.err || { tail $out/${i}_$v.err; exit 1; }
   python tools/bench_summary.py $out/${i}_$v.json | sed "s/^/$var=$v /"
 done

@@ -7,7 +7,7 @@ mkdir -p "$R/$out"
 export TMPDIR=/tmp
 for c in "$@"; do
   (cd /tmp && timeout -k 10 300 rocprofv3 --kernel-trace --stats -f csv -d "$R/$out/tr_$c" -o run -- \
-    python3 "$R/bench.py" --no-cpu-baseline --config $c --steps 30 > "$R/$out/b_$c.json" 2> "$R/$out/b_$c.err") || exit 1
+    python3 "$R/bench.py" --full --no-cpu-baseline --config $c --steps 30 > "$R/$out/b_$c.json" 2> "$R/$out/b_$c.err") || exit 1
   f=$(ls "$R/$out"/tr_$c/*/run_kernel_trace.csv 2>/dev/null | head -1)
   [ -z "$f" ] && f=$(find "$R/$out/tr_$c" -name "*kernel_trace.csv" | head -1)
   python3 "$R/tools/timeline.py" "$f" --step 20 > "$R/$out/timeline_$c.txt" || exit 1

@@ -15,7 +15,7 @@ mkdir -p "$out"
 export TMPDIR=/tmp
 cd /tmp || exit 1
 timeout -k 10 420 rocprofv3 --kernel-trace --stats -f csv -d "$out/stats" -o run -- \
-  python3 "$R/bench.py" --no-cpu-baseline "$@" > "$out/bench.json" 2> "$out/bench.err" || exit 1
+  python3 "$R/bench.py" --full --no-cpu-baseline "$@" > "$out/bench.json" 2> "$out/bench.err" || exit 1
 echo "[profile] $name stats done"
 # the PMC passes re-run the stats run's GEMM choices (the tuner's probes would
 # time differently under counters and could pick other kernels)
@@ -26,7 +26,7 @@ for pass in FETCH_SIZE WRITE_SIZE "SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE SQ_B
   tag=${pass%% *}
   # shellcheck disable=SC2086
   timeout -s KILL 420 rocprofv3 --pmc $pass -f csv -d "$out/pmc_$tag" -o run -- \
-    python3 "$R/bench.py" --no-cpu-baseline --steps 5 --warmup 2 "$@" > "$out/pmc_$tag.json" \
+    python3 "$R/bench.py" --full --no-cpu-baseline --steps 5 --warmup 2 "$@" > "$out/pmc_$tag.json" \
     2> "$out/pmc_$tag.err" || exit 1
   echo "[profile] $name pmc $tag done"
 done
