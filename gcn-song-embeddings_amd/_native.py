@@ -94,6 +94,9 @@ _SIGS = {
                                        vp, vp, i64, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                        ctypes.c_int, ctypes.c_int, vp]),
     "pinsage_weighted_agg": (ctypes.c_int, [vp, i64, vp, vp, i64, i64, vp, vp]),
+    "pinsage_agg_transpose_scratch_bytes": (i64, [i64, i64, i64, i64]),
+    "pinsage_agg_transpose": (ctypes.c_int, [vp, vp, vp, i64, i64, vp, i64, vp, i64, vp, i64, ctypes.c_int, vp, vp,
+                                             vp, i64, vp]),
     "pinsage_conv_agg_project": (ctypes.c_int, [vp, i64, i64, vp, vp, i64, i64, vp, vp, i64, i64, vp, vp,
                                                 i64, vp, vp, vp, vp, vp]),
     "pinsage_gather_rows": (ctypes.c_int, [vp, i64, i64, i64, vp, i64, vp, i64, vp]),

@@ -57,6 +57,15 @@ int launch_set_rank_table(const int64_t*, int64_t, const int32_t*, int64_t, int,
                           const uint32_t*, int32_t*, hipStream_t);
 int launch_norm_lrelu_bwd(const float*, const float*, const float*, int, const int*, int64_t, float*, float*,
                           int, const int*, int*, int64_t, hipStream_t);
+int csr_prepare();
+int launch_csr_build(const int32_t*, const float*, const int*, int64_t, int, const int*, int64_t, int*, int*,
+                     int*, int*, int*, int2*, int2*, int*, int2*, int*, float*, int, hipStream_t, int2*);
+int64_t dq_chunk_capacity(int64_t, int, int64_t);
+int64_t dq_split_capacity(int64_t, int);
+int dq_tree_levels(int64_t max_chunks);
+int launch_dq_chunks(const int2*, const int*, int64_t, const int2*, const int*, int64_t, const int*,
+                     const int2*, const float*, int64_t, const float*, int, float*, float*, hipStream_t,
+                     const int32_t*, int32_t*, const int*, int*, uint16_t*, int64_t);
 int64_t knn_scratch_bytes(int64_t, int64_t);
 int launch_knn_cosine(const float*, int64_t, int64_t, int64_t, const int64_t*, int64_t, int64_t,
                       float, void*, int64_t, float*, int64_t*, int*, hipStream_t);
@@ -789,6 +798,78 @@ int pinsage_knn_cosine(const float* emb, int64_t n, int64_t d, int64_t ld, const
 int pinsage_weighted_agg(const float* q, int64_t hid, const int32_t* loc, const float* w,
                          int64_t n_rows, int64_t T, float* agg, void* stream) {
   return launch_agg(q, (int)hid, loc, w, (int)T, nullptr, n_rows, agg, (hipStream_t)stream);
+}
+
+// scratch of pinsage_agg_transpose: the buffers the engine carves per layer
+// for its CSR transpose and dq chunk list (engine.hip, LayerBuf), same sizes
+struct AggTScratch {
+  int64_t cnt, bsum, off, cursor, cbase, occ2, occ2b, chunks, nchunks, split, nsplit, part, tk, bytes;
+  int64_t max_chunks, max_split;
+};
+static bool agg_transpose_shape_ok(int64_t S, int64_t T, int64_t N, int64_t hid) {
+  return S >= 1 && T >= 1 && T <= 64 && N >= 1 && hid >= 4 && hid % 4 == 0 && hid <= 65536 &&
+         S * T <= INT32_MAX - 64 && N <= INT32_MAX - 64;
+}
+static AggTScratch agg_transpose_layout(int64_t S, int64_t T, int64_t N, int64_t hid) {
+  AggTScratch a{};
+  int64_t cur = 0;
+  auto carve = [&cur](int64_t bytes) {
+    const int64_t at = cur;
+    cur += align_up(bytes, 256);
+    return at;
+  };
+  a.max_chunks = dq_chunk_capacity(S, (int)T, N);
+  a.max_split = dq_split_capacity(S, (int)T);
+  a.cnt = carve((N + 1) * 4);
+  a.tk = carve((int64_t)dq_tree_levels(a.max_chunks) * a.max_chunks * 4);
+  a.bsum = carve((int64_t)ceil_div(N + 1, 1024) * 8 + 16);
+  a.off = carve((N + 1) * 4);
+  a.cursor = carve((N + 1) * 4);
+  a.cbase = carve((N + 1) * 4);
+  a.occ2 = carve(a.max_chunks * 16 * 8);
+  a.occ2b = carve(a.max_chunks * 16 * 8);
+  a.chunks = carve(a.max_chunks * 8);
+  a.nchunks = carve(16);
+  a.split = carve(a.max_split * 8);
+  a.nsplit = carve(16);
+  a.part = carve(a.max_chunks * hid * 4);
+  a.bytes = cur;
+  return a;
+}
+
+int64_t pinsage_agg_transpose_scratch_bytes(int64_t n_rows_max, int64_t T, int64_t n_q_max, int64_t hid) {
+  if (!agg_transpose_shape_ok(n_rows_max, T, n_q_max, hid)) return -1;
+  return agg_transpose_layout(n_rows_max, T, n_q_max, hid).bytes;
+}
+
+int pinsage_agg_transpose(const int32_t* loc, const float* w, const int* n_rows_dev, int64_t n_rows_max, int64_t T,
+                          const int* n_q_dev, int64_t n_q_max, const float* dagg, int64_t ld_dagg, const float* q,
+                          int64_t hid, int mode, void* scratch, float* dpq, uint16_t* dpq_planes,
+                          int64_t plane_stride, void* stream) {
+  PS_REQUIRE(agg_transpose_shape_ok(n_rows_max, T, n_q_max, hid), kErrArg,
+             "agg_transpose: needs 1 <= T <= 64, hid a multiple of 4, row and slot counts below 2^31");
+  PS_REQUIRE(loc && w && n_rows_dev && n_q_dev && dagg && q && scratch && dpq, kErrArg,
+             "agg_transpose: null pointer");
+  PS_REQUIRE(ld_dagg >= hid && ld_dagg % 4 == 0, kErrArg, "agg_transpose: ld_dagg must be a multiple of 4 >= hid");
+  PS_REQUIRE(mode == 0 || (mode == 1 && hid <= 512), kErrArg,
+             "agg_transpose: mode is 0 (combine kernel) or 1 (split-row tree, hid <= 512)");
+  PS_REQUIRE(!dpq_planes || (mode == 1 && plane_stride >= n_q_max * hid && plane_stride % 4 == 0), kErrArg,
+             "agg_transpose: planes output needs mode 1 (hid <= 512) and a plane stride >= n_q_max * hid, "
+             "a multiple of 4");
+  const AggTScratch a = agg_transpose_layout(n_rows_max, T, n_q_max, hid);
+  char* sc = static_cast<char*>(scratch);
+  auto at_i = [sc](int64_t o) { return reinterpret_cast<int*>(sc + o); };
+  auto at_2 = [sc](int64_t o) { return reinterpret_cast<int2*>(sc + o); };
+  hipStream_t st = (hipStream_t)stream;
+  PS_TRY(csr_prepare());
+  PS_TRY(launch_csr_build(loc, w, n_rows_dev, n_rows_max, (int)T, n_q_dev, n_q_max, at_i(a.cnt), at_i(a.bsum),
+                          at_i(a.off), at_i(a.cursor), at_i(a.cbase), at_2(a.occ2), at_2(a.chunks),
+                          at_i(a.nchunks), at_2(a.split), at_i(a.nsplit), dpq, (int)hid, st, at_2(a.occ2b)));
+  return launch_dq_chunks(at_2(a.chunks), at_i(a.nchunks), a.max_chunks, at_2(a.split), at_i(a.nsplit),
+                          a.max_split, at_i(a.off), at_2(a.occ2), dagg, ld_dagg, q, (int)hid, dpq,
+                          reinterpret_cast<float*>(sc + a.part), st, nullptr, nullptr,
+                          mode == 1 ? at_i(a.cbase) : nullptr, mode == 1 ? at_i(a.tk) : nullptr, dpq_planes,
+                          plane_stride);
 }
 
 int64_t pinsage_fly_workspace_bytes(int64_t n, int64_t B, int64_t n_layers, int64_t T, int64_t n_hops) {

@@ -738,9 +738,16 @@ typedef int dq_v4i __attribute__((ext_vector_type(4)));
 // registers (bf16split.h), so its planes form (wgrad_pl_kernel) gets the same
 // products
 __device__ __forceinline__ void dq_store_planes(uint16_t* __restrict__ base, int64_t ps, int64_t e, float4 v) {
+  // The planes are the split of the ROUNDED fp32 value.  The tree's root hands
+  // in acc * lrelu'(q) straight from the multiply, and the compiler contracted
+  // that multiply into the split's first subtraction (v_pk_fma: the residual
+  // of the unrounded product), so M and L were not split_planes' of the fp32
+  // result where the slope is 0.01.  Opaque registers keep the product rounded.
+  float a = v.x, b = v.y, c = v.z, d = v.w;
+  asm("" : "+v"(a), "+v"(b), "+v"(c), "+v"(d));
   unsigned h0, m0, l0, h1, m1, l1;
-  split_pair(f32x2{v.x, v.y}, h0, m0, l0);
-  split_pair(f32x2{v.z, v.w}, h1, m1, l1);
+  split_pair(f32x2{a, b}, h0, m0, l0);
+  split_pair(f32x2{c, d}, h1, m1, l1);
   *reinterpret_cast<uint2*>(base + e) = make_uint2(h0, h1);
   *reinterpret_cast<uint2*>(base + ps + e) = make_uint2(m0, m1);
   *reinterpret_cast<uint2*>(base + 2 * ps + e) = make_uint2(l0, l1);

@@ -680,6 +680,13 @@ class _DeviceTable:
             # the reference's h[nb] raises IndexError for these (collection ids
             # in the zero-weight tail of a tiny graph)
             raise IndexError("neighbourhood table references ids >= n_items")
+        # the backward's transposed aggregation sorts each neighbour's pairs by
+        # node and needs them distinct (pinsage_engine_set_tensors): a top-k
+        # row never repeats an id, a hand-made table might
+        for r0 in range(0, int(nb_t.shape[0]), 1 << 20):
+            s = nb_t[r0:r0 + (1 << 20)].sort(1).values
+            if bool((s[:, 1:] == s[:, :-1]).any()):
+                raise ValueError("neighbourhood table repeats an id inside a row's first T entries")
         self.nb32 = nb_t.to(torch.int32).contiguous().to(dev)
         self.wn = (w_t / w_t.sum(1, keepdim=True)).to(torch.float32).contiguous().to(dev)
 

@@ -317,6 +317,47 @@ int pinsage_linear_ilv(const uint16_t* A_ilv, int64_t lda_ilv, const int32_t* a_
  * pinsage_model.py:202). */
 int pinsage_weighted_agg(const float* q, int64_t hid, const int32_t* loc, const float* w,
                          int64_t n_rows, int64_t T, float* agg, void* stream);
+/* The transpose of that aggregation -- the backward of pinsage_model.py:202 with
+ * respect to the q rows, through the LeakyReLU that produced them: for each q
+ * row u in [0, *n_q_dev)
+ *   dpq[u] = lrelu'(q[u]) * sum over the slots (f, t) with loc[f][t] == u of
+ *            w[f][t] * dagg[f]
+ * by the engine's own launches in the engine's order: the CSR transpose of the
+ * slot table by q row with its chunk list (<= 16 slots per chunk) and the
+ * canonical order of every q row's pairs (sorted by source row f), then the
+ * chunk kernel.  mode 0: rows split over several chunks are summed by the
+ * combine kernel; mode 1 (hid <= 512): by the fan-in-8 tree inside the chunk
+ * kernel.  Both sum a row in a fixed order (bitwise reproducible).
+ * The counts are device-side below static capacities, as in the engine:
+ * *n_rows_dev <= n_rows_max source rows, *n_q_dev <= n_q_max q rows (the
+ * capacities size the scratch and the grids, and choose the scan kernel).
+ * loc int32 / w f32 [*n_rows_dev][T], 1 <= T <= 64; dagg f32 rows of stride
+ * ld_dagg >= hid (a multiple of 4); q, dpq f32 [*n_q_dev][hid], hid % 4 == 0.
+ * Preconditions the kernels do NOT check: every loc value lies in
+ * [0, *n_q_dev), and the T entries of a row of loc are distinct (a q row's
+ * source rows are distinct -- see pinsage_engine_set_tensors; a repeated
+ * (u, f) pair leaves slots of the sorted pair list unwritten, whose stale
+ * contents are then used as row indices into dagg).
+ * A q row that occurs in no slot has no chunk: its dpq row is NOT written (the
+ * engine's frontier only holds q rows that occur in a slot).
+ * dpq_planes (nullable; mode 1 only): the result as hi / mid / lo bf16 planes
+ * [3][plane_stride] (plane_stride >= n_q_max * hid elements, a multiple of 4;
+ * row u at u * hid) -- bitwise pinsage_split_planes of the fp32 result --
+ * INSTEAD of dpq, which is then not written.
+ * scratch: pinsage_agg_transpose_scratch_bytes(n_rows_max, T, n_q_max, hid)
+ * bytes (-1 for shapes the entry rejects), 256-B aligned: the per-row counters
+ * cnt, the scan's block sums, off, cursor, cbase, the pair lists occ2 and
+ * occ2b (the sort's second buffer), the chunk and split-row lists with their
+ * counts, the split rows' partial sums and the tree's tickets, with the sizes
+ * the engine carves per layer.  Zero it once before the first call: the scan
+ * leaves cnt zero behind its read and the tree's tickets reset themselves, so
+ * later calls on the same scratch (any mode) need no clearing.  Raises the
+ * CSR kernels' dynamic-LDS limit on first use (not capturable). */
+int64_t pinsage_agg_transpose_scratch_bytes(int64_t n_rows_max, int64_t T, int64_t n_q_max, int64_t hid);
+int pinsage_agg_transpose(const int32_t* loc, const float* w, const int* n_rows_dev, int64_t n_rows_max, int64_t T,
+                          const int* n_q_dev, int64_t n_q_max, const float* dagg, int64_t ld_dagg, const float* q,
+                          int64_t hid, int mode, void* scratch, float* dpq, uint16_t* dpq_planes,
+                          int64_t plane_stride, void* stream);
 
 /* ConvLayer.forward after the Q projection (pinsage_model.py:195-210): for each
  * row f of n_rows,
@@ -474,7 +515,14 @@ int64_t pinsage_engine_num_params(const pinsage_engine* e);
 int pinsage_engine_offsets(const pinsage_engine* e, pinsage_engine_offsets_t* out);
 /* features f32 [n_items][ld_feats]; tables: nb int32 / normalised weights f32
  * [n_items][ld_table] (first T columns used); grads / adam buffers may be null
- * for inference. */
+ * for inference.
+ * Precondition (not checked here: the table is device memory): the first T
+ * entries of every row of nb_table are distinct, as the rows of a top-k are.
+ * The backward's transposed aggregation sorts each neighbour's (node, weight)
+ * pairs by node and relies on that: a node repeated inside one row loses a
+ * pair in rows of 17-64 pairs and leaves unwritten row indices in longer ones
+ * (see pinsage_agg_transpose).  pinsage_model checks a table once on the host
+ * where it is bound (_DeviceTable raises ValueError). */
 int pinsage_engine_set_tensors(pinsage_engine* e, const float* feats, int64_t ld_feats,
                                const int32_t* nb_table, const float* w_table, int64_t ld_table,
                                float* params, float* grads, float* adam_m, float* adam_v);
@@ -585,7 +633,9 @@ int pinsage_engine_set_hints(pinsage_engine* e, const int64_t* S, const int64_t*
  * the engine-wide one from pinsage_engine_set_tensors: the on-the-fly sampler
  * (relevant_nodes_per_layer, pinsage_model.py:142-154) draws every layer's
  * neighbourhoods separately.  nb = wn = null restores the engine-wide table.
- * Read when a frontier is enqueued (pinsage_engine_forward / _frontier). */
+ * Read when a frontier is enqueued (pinsage_engine_forward / _frontier).
+ * Precondition, as pinsage_engine_set_tensors: the first T entries of every
+ * used row of nb are distinct (the sampler's top-k rows are); not checked. */
 /* Whether a GEMM site's last launch ran stream-K (1), a whole-K tile (0), or
  * is unknown (-1): the in-context tuner keeps a site's summation order. */
 int pinsage_engine_site_stream_k(const pinsage_engine* e, const char* site);

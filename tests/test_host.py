@@ -244,6 +244,23 @@ def test_compute_fails_loudly_without_gpu():
         pm.do_random_walks(g, torch.tensor([0]), 3, 0.85)
 
 
+def test_device_table_refuses_an_id_repeated_inside_a_row():
+    """The transposed aggregation's canonical sorts need a node's first T
+    neighbours distinct (pinsage_engine_set_tensors): a hand-made table that
+    repeats one is refused on the host, where it is bound; a repeat past column
+    T is not the model's business."""
+    import pinsage_model as pm
+    w = torch.rand(6, 4, dtype=torch.float64) + 0.1
+    nb = torch.tensor([[1, 2, 3, 4], [0, 2, 3, 5], [5, 4, 3, 1], [0, 1, 2, 4], [3, 2, 1, 0], [4, 3, 2, 1]])
+    t = pm._DeviceTable((w, nb), 3, 6, "cpu")
+    assert t.nb32.dtype == torch.int32 and tuple(t.nb32.shape) == (6, 3)
+    nb[4, 3] = 3  # a repeat outside the first T columns
+    pm._DeviceTable((w, nb), 3, 6, "cpu")
+    nb[4, 2] = 3  # row 4 = 3, 2, 3, 3
+    with pytest.raises(ValueError, match="repeats an id"):
+        pm._DeviceTable((w, nb), 3, 6, "cpu")
+
+
 def test_batch_sampler_speculation_is_exact():
     """The native sampler's speculative next batch is used only when torch's
     generator is untouched in between; batches, nodesets and the generator
