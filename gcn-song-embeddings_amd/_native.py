@@ -40,6 +40,13 @@ class EngineOffsets(ctypes.Structure):
                 ("hinge", i64)]
 
 
+class EnginePlanOffsets(ctypes.Structure):
+    """pinsage_engine_plan_offsets_t: where a workspace keeps the frontier's
+    index tables and position CSR (read back by the tests)."""
+    _fields_ = [("self_src", i64 * 8), ("q_src", i64 * 8), ("loc", i64 * 8), ("wloc", i64 * 8),
+                ("rank_off", i64), ("pos_sorted", i64)]
+
+
 # name -> (restype, argtypes)
 _SIGS = {
     "pinsage_version": (ctypes.c_int, []),
@@ -135,6 +142,7 @@ _SIGS = {
     "pinsage_engine_init_workspace": (i32, [vp, vp, vp]),
     "pinsage_engine_num_params": (i64, [vp]),
     "pinsage_engine_offsets": (ctypes.c_int, [vp, ctypes.POINTER(EngineOffsets)]),
+    "pinsage_engine_plan_offsets": (ctypes.c_int, [vp, ctypes.POINTER(EnginePlanOffsets)]),
     "pinsage_engine_set_tensors": (ctypes.c_int, [vp, vp, i64, vp, vp, i64, vp, vp, vp, vp]),
     "pinsage_engine_set_feature_planes": (ctypes.c_int, [vp, vp, i64]),
     "pinsage_engine_set_frontier_fork": (ctypes.c_int, [vp, ctypes.c_int]),

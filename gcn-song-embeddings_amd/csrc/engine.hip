@@ -1495,6 +1495,25 @@ int pinsage_engine_offsets(const pinsage_engine* e, pinsage_engine_offsets_t* o)
   return kOk;
 }
 
+int pinsage_engine_plan_offsets(const pinsage_engine* e, pinsage_engine_plan_offsets_t* o) {
+  if (!e || !o) {
+    set_error("engine_plan_offsets: null argument");
+    return kErrArg;
+  }
+  const Engine* E = reinterpret_cast<const Engine*>(e);
+  *o = pinsage_engine_plan_offsets_t{};
+  for (int64_t l = 0; l < E->cfg.n_layers && l < 8; ++l) {
+    const LayerBuf& lb = E->L[(size_t)l];
+    o->self_src[l] = (int64_t)lb.self_src;
+    o->q_src[l] = (int64_t)lb.q_src;
+    o->loc[l] = (int64_t)lb.loc;
+    o->wloc[l] = (int64_t)lb.wloc;
+  }
+  o->rank_off = (int64_t)E->rank_off;
+  o->pos_sorted = (int64_t)E->pos_sorted;
+  return kOk;
+}
+
 int pinsage_engine_timing(pinsage_engine* e, int enable) {
   Engine* E = reinterpret_cast<Engine*>(e);
   for (auto& t : E->sites)

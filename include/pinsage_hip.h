@@ -217,6 +217,28 @@ int pinsage_frontier_local_idx(const int64_t* nodeset, int64_t n, const int32_t*
 int pinsage_linear(const float* A, int64_t lda, const int32_t* a_idx, int64_t M, int64_t K,
                    const float* W, const float* bias, int64_t N, int act, float* C, int64_t ldc,
                    void* stream);
+/* (the train-step engine's handle, see "train-step engine" below) */
+typedef struct pinsage_engine pinsage_engine;
+/* The train-step engine's frontier plan, for tests that read it back: the
+ * workspace byte offsets of what pinsage_engine_frontier builds beside the
+ * sets that pinsage_engine_offsets_t already locates.  Per layer l (index 0 =
+ * bottom; |S_l|, |N_l| live entries, from count_S / count_N):
+ *   self_src int32 [|S_l|]     row of S_l[f] in S_{l-1} (layer 0: the id itself)
+ *   q_src    int32 [|N_l|]     row of N_l[u] in S_{l-1} (layer 0: the id itself)
+ *   loc      int32 [|S_l|][T]  rank of nb[S_l[f]][t] in N_l
+ *   wloc     f32   [|S_l|][T]  wn[S_l[f]][t], copied bit for bit
+ * and the batch positions grouped by their top-set rank:
+ *   rank_off   int32 [|S_top| + 1]  rank r's positions are pos_sorted[rank_off[r]
+ *                                   .. rank_off[r + 1]); rank_off[0] = -1: absent
+ *                                   (more than 16384 positions)
+ *   pos_sorted int32 [n_ids]        positions by (pos_rank, position)
+ * A struct of its own: pinsage_engine_offsets_t keeps its size for callers
+ * compiled against it.  Entries of layers >= n_layers are 0. */
+typedef struct {
+  int64_t self_src[8], q_src[8], loc[8], wloc[8];
+  int64_t rank_off, pos_sorted;
+} pinsage_engine_plan_offsets_t;
+int pinsage_engine_plan_offsets(const pinsage_engine* e, pinsage_engine_plan_offsets_t* out);
 /* General form of the same GEMM, for per-configuration tests and
  * microbenchmarks: C = op(A) op(B) with A K-major ([M][K], rows gathered by
  * a_idx) or M-major ([K][M], k-rows gathered), B K-major ([N][K]) or N-major
@@ -484,7 +506,6 @@ int pinsage_knn_cosine(const float* emb, int64_t n, int64_t d, int64_t ld, const
  * one flat fp32 buffer in state_dict order: conv_layers.{i}.Q.weight, Q.bias,
  * W.weight, W.bias (i = 0..n_layers-1), G1.weight, G1.bias, G2.weight; the
  * gradient and Adam buffers use the same layout. */
-typedef struct pinsage_engine pinsage_engine;
 typedef struct {
   int64_t n_items;  /* feature-table rows (tracks) */
   int64_t d_in;     /* feature dim (dimensions[0]) */

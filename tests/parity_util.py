@@ -270,3 +270,89 @@ def fixed_cotangent_check(model, feats, ids, w, nb, L, T, seed=0, tol=1e-4, cond
     assert fwd <= tol, fwd
     assert max(errs.values()) <= tol, errs
     return fwd, errs
+
+
+# ----------------------------------------------------------------------------- frontier plan
+# The integer plan pinsage_engine_frontier builds (tests/test_gpu_frontier_plan.py
+# reads it from a workspace; tests/test_host.py checks that the comparison can
+# fail).  A plan is a dict:
+#   layers[l]  count_S, count_N (the device-side counts), S, N (sorted member
+#              lists up to their count), loc / wloc [|S|][T] (wloc as uint32
+#              bits), self_src [|S|], q_src [|N|]            -- l = 0 is the bottom
+#   read_counts  (|S_l| list, |N_l| list) as pinsage_engine_read_counts gives them
+#   pos_rank [n_pos]; rank_off [|S_top| + 1] (or [-1]: position CSR absent,
+#   more than POS_CSR_MAX positions); pos_sorted [n_pos]
+POS_CSR_MAX = 16384  # kPosCsrMax (conv.hip)
+PLAN_LAYER_FIELDS = ("count_S", "S", "count_N", "N", "loc", "wloc", "self_src", "q_src")
+
+
+def frontier_plan_reference(ids, rows, n_layers, T, virtual=None):
+    """The plan in int64 numpy, top down, from the ids and the table rows of the
+    reference's own sets only: rows(l, S) -> (nb[S, :T] as int64, wn[S, :T] as
+    uint32 bits) of layer l's table.  virtual = (x0, n_x): the ids x0 .. x0 +
+    n_x - 1 join the top set (pinsage_engine_set_fly)."""
+    ids = np.asarray(ids, np.int64).reshape(-1)
+    top = ids if not virtual else np.concatenate([ids, np.arange(virtual[0], virtual[0] + virtual[1], dtype=np.int64)])
+    S = np.unique(top)
+    layers = [None] * n_layers
+    for l in range(n_layers - 1, -1, -1):
+        nb, w = rows(l, S)
+        nb = np.asarray(nb, np.int64).reshape(len(S), T)
+        N = np.unique(nb)
+        layers[l] = {"count_S": len(S), "S": S, "count_N": len(N), "N": N,
+                     "loc": np.searchsorted(N, nb), "wloc": np.asarray(w, np.uint32).reshape(len(S), T)}
+        S = np.unique(np.concatenate([N, S]))
+    for l, lay in enumerate(layers):
+        below = layers[l - 1]["S"] if l else None
+        for dst, src in (("self_src", "S"), ("q_src", "N")):
+            lay[dst] = np.searchsorted(below, lay[src]) if l else lay[src].copy()
+    S_top = layers[-1]["S"]
+    pos_rank = np.searchsorted(S_top, ids)
+    plan = {"layers": layers, "pos_rank": pos_rank,
+            "read_counts": ([lay["count_S"] for lay in layers], [lay["count_N"] for lay in layers])}
+    if len(ids) > POS_CSR_MAX:
+        plan["rank_off"] = np.array([-1], np.int64)
+        plan["pos_sorted"] = None
+    else:
+        order = np.argsort(pos_rank, kind="stable")
+        plan["pos_sorted"] = order.astype(np.int64)
+        plan["rank_off"] = np.searchsorted(pos_rank[order], np.arange(len(S_top) + 1), side="left")
+    return plan
+
+
+def _plan_field(where, field, got, want):
+    got = np.asarray(got)
+    want = np.asarray(want)
+    if got.dtype.kind == "f" or want.dtype.kind == "f":
+        raise AssertionError(f"{where} {field}: compare floats as bits")
+    g = got.astype(np.int64).reshape(-1)
+    w = want.astype(np.int64).reshape(-1)
+    if field == "wloc":  # bit patterns: int32 and uint32 views of one word are equal
+        g, w = g & 0xFFFFFFFF, w & 0xFFFFFFFF
+    if g.shape != w.shape:
+        raise AssertionError(f"{where} {field}: {g.shape[0]} entries, reference has {w.shape[0]}")
+    bad = np.flatnonzero(g != w)
+    if len(bad):
+        i = int(bad[0])
+        raise AssertionError(f"{where} {field}: {len(bad)} of {len(w)} entries differ, first at [{i}]: "
+                             f"got {int(g[i])} (0x{int(g[i]) & 0xffffffff:08x}), "
+                             f"reference {int(w[i])} (0x{int(w[i]) & 0xffffffff:08x})")
+
+
+def check_frontier_plan(got, want):
+    """Exact, element for element (wloc bit for bit); the first difference,
+    top down, raises an AssertionError naming the layer and the field."""
+    L = len(want["layers"])
+    if len(got["layers"]) != L:
+        raise AssertionError(f"plan: {len(got['layers'])} layers, reference has {L}")
+    for l in range(L - 1, -1, -1):
+        for f in PLAN_LAYER_FIELDS:
+            _plan_field(f"layer {l}", f, got["layers"][l][f], want["layers"][l][f])
+    for k, name in ((0, "S"), (1, "N")):
+        _plan_field("all layers", f"read_counts {name}", got["read_counts"][k], want["read_counts"][k])
+    _plan_field("positions", "pos_rank", got["pos_rank"], want["pos_rank"])
+    if int(np.asarray(want["rank_off"]).reshape(-1)[0]) == -1:  # absent: only the mark is defined
+        _plan_field("positions", "rank_off", np.asarray(got["rank_off"]).reshape(-1)[:1], [-1])
+        return
+    _plan_field("positions", "rank_off", got["rank_off"], want["rank_off"])
+    _plan_field("positions", "pos_sorted", got["pos_sorted"], want["pos_sorted"])

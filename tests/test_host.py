@@ -401,6 +401,76 @@ def test_torch_operator_library_registers_every_op():
         torch.ops.pinsage.linear(x, None, W, None, True)
 
 
+def test_frontier_plan_checker_rejects_single_defects():
+    """parity_util.check_frontier_plan (the comparison behind
+    tests/test_gpu_frontier_plan.py) passes a correct plan and names the layer
+    and the field of each single defect."""
+    import copy
+    from parity_util import check_frontier_plan, frontier_plan_reference
+    rng = np.random.default_rng(17)
+    n, L, T = 900, 2, 3
+    nb = np.argsort(rng.random((n, 40)), 1)[:, :T] * 22 + rng.integers(0, 20, (n, 1))  # distinct within a row
+    wb = rng.integers(0, 1 << 32, (n, T), dtype=np.uint64).astype(np.uint32)
+    assert nb.max() < n
+    ids = rng.integers(0, n, 50)
+    want = frontier_plan_reference(ids, lambda l, S: (nb[S], wb[S]), L, T)
+    # the reference against the definitions, on this small case
+    top = want["layers"][1]
+    assert np.array_equal(top["S"], np.unique(ids)) and np.array_equal(top["S"][want["pos_rank"]], ids)
+    assert np.array_equal(top["N"][top["loc"]], nb[top["S"]])
+    assert np.array_equal(want["layers"][0]["S"][top["q_src"]], top["N"])
+    assert np.array_equal(want["layers"][0]["S"][top["self_src"]], top["S"])
+    assert np.array_equal(want["layers"][0]["q_src"], want["layers"][0]["N"])
+    for r in range(len(top["S"])):
+        p = want["pos_sorted"][want["rank_off"][r]:want["rank_off"][r + 1]]
+        assert np.array_equal(p, np.flatnonzero(ids == top["S"][r]))
+    check_frontier_plan(copy.deepcopy(want), want)
+
+    def defect(change, match):
+        got = copy.deepcopy(want)
+        change(got)
+        with pytest.raises(AssertionError, match=match):
+            check_frontier_plan(got, want)
+
+    def off_by_one(p):
+        p["layers"][1]["loc"][7, 1] += 1
+
+    def swapped(p):
+        S = p["layers"][0]["S"]
+        S[[4, 5]] = S[[5, 4]]
+
+    def missing(p):
+        lay = p["layers"][0]
+        lay["N"] = np.delete(lay["N"], 11)
+        lay["count_N"] -= 1
+
+    def shifted(p):
+        p["rank_off"][9] += 1
+
+    def one_bit(p):
+        p["layers"][0]["wloc"][20, 2] ^= np.uint32(1 << 22)
+
+    def stale_read_counts(p):
+        p["read_counts"] = (p["read_counts"][0], [p["read_counts"][1][0], p["read_counts"][1][1] + 1])
+
+    defect(off_by_one, r"^layer 1 loc: 1 of \d+ entries differ, first at \[22\]")
+    defect(swapped, r"^layer 0 S: 2 of \d+ entries differ, first at \[4\]")
+    defect(missing, r"^layer 0 count_N: 1 of 1 entries differ")
+    defect(shifted, r"^positions rank_off: 1 of \d+ entries differ, first at \[9\]")
+    defect(one_bit, r"^layer 0 wloc: 1 of \d+ entries differ, first at \[62\]")
+    defect(stale_read_counts, r"^all layers read_counts N: ")
+    # more than 16384 positions: the position CSR is absent, only its mark is compared
+    many = rng.integers(0, n, 16385)
+    absent = frontier_plan_reference(many, lambda l, S: (nb[S], wb[S]), L, T)
+    assert absent["rank_off"].tolist() == [-1]
+    got = copy.deepcopy(absent)
+    got["rank_off"] = np.array([-1, 123, 456])
+    check_frontier_plan(got, absent)
+    got["rank_off"] = np.array([0, 123, 456])
+    with pytest.raises(AssertionError, match="^positions rank_off"):
+        check_frontier_plan(got, absent)
+
+
 def test_bench_refuses_a_world_size_other_than_gpus():
     """bench.py started by a launcher with WORLD_SIZE != --gpus exits non-zero
     before touching the GPU (launch_ranks)."""
