@@ -412,6 +412,9 @@ int launch_knn_cosine(const float* emb, int64_t n, int64_t d, int64_t ld, const 
                       float* out_w, int64_t* out_n, int* err, hipStream_t st) {
   PS_REQUIRE(n > 0 && d > 0 && ld >= d && nq >= 0, kErrArg, "knn: bad sizes");
   PS_REQUIRE(d % 4 == 0, kErrArg, "knn: d must be a multiple of 4");
+  // the GEMM reads rows in 16-byte pieces straight into LDS: every row starts aligned
+  PS_REQUIRE(ld % 4 == 0 && (reinterpret_cast<uintptr_t>(emb) & 15) == 0, kErrArg,
+             "knn: ld must be a multiple of 4 and emb 16-byte aligned");
   PS_REQUIRE(n <= INT32_MAX && d <= INT32_MAX, kErrArg, "knn: table too large");
   PS_REQUIRE(k >= 1 && k <= n && k <= kKnnMaxK, kErrArg, "knn: need 1 <= k <= min(n, 4096)");
   if (nq == 0) return kOk;

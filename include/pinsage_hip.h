@@ -491,7 +491,10 @@ int pinsage_segment_wmean(const float* h, int64_t ldh, int64_t n_h, int64_t d, c
  *   sim(q, j) = dot(emb[q], emb[j]) / (|emb[q]| |emb[j]| + eps), j in [0, n)
  * out_w f32 [nq][k] / out_n int64 [nq][k]: the k largest, sorted descending
  * (exact ties: lower index first).  The reference then drops column 0.
- * emb: f32 device rows of stride ld (d % 4 == 0); 1 <= k <= min(n, 4096).
+ * emb: f32 device rows of stride ld floats, 16-byte aligned (d % 4 == 0,
+ * ld >= d and ld % 4 == 0: rows are read in 16-byte pieces; the ld - d floats
+ * after a row are never read); 1 <= k <= min(n, 4096).  A refused call
+ * (PINSAGE_ERR_ARG, PINSAGE_ERR_WORKSPACE) launches nothing.
  * scratch: device bytes >= pinsage_knn_scratch_bytes(n, rows) for some
  * batch of rows >= 1 (the dot products of one batch of queries live there;
  * larger scratch = fewer batches). */

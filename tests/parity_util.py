@@ -356,3 +356,270 @@ def check_frontier_plan(got, want):
         return
     _plan_field("positions", "rank_off", got["rank_off"], want["rank_off"])
     _plan_field("positions", "pos_sorted", got["pos_sorted"], want["pos_sorted"])
+
+
+# ----------------------------------------------------------------------------- cosine kNN selection
+# pinsage_knn_cosine's per-row selection (knn_select_kernel, csrc/knn.hip) on
+# tables whose similarities are exact in fp32 (tests/test_gpu_knn_select.py
+# compares ids and value bits; tests/test_host.py checks that every case
+# reaches the exit it was built for and that the comparison can fail).
+#
+# Rows are (x_j, KNN_Y, 0, ..., 0) with integer x_j, d = 16, plus the probe
+# rows (1, 0, ...), (-1, 0, ...), (2, 0, ...) and an all-zero row; queries are
+# probe rows only.  Each dot product then has one non-zero term, an integer
+# below 2^24 (exact in the fp32 MFMA chain and in the split-bf16 products: a
+# 15-bit integer is its hi + mid planes, a probe a single hi value), the norms
+# are float32(sqrt(an exact double)), and |q| |e_j| + eps is |e_j|, 2 |e_j| or
+# eps: each similarity is one IEEE fp32 division.
+KNN_SAMPLE = 4096    # kKnnSample (knn.hip): leading keys that set the candidate threshold
+KNN_SEG = 512        # kKnnSeg: candidate slots per wave
+KNN_WAVES = 16       # kKnnBlock / 64: waves of the selection's workgroup
+KNN_MAX_SORT = 4096  # kKnnMaxK: most keys the in-LDS sort takes
+KNN_BLOCK = 64 * KNN_WAVES
+KNN_D = 16
+KNN_Y = 3000
+KNN_PROBES = ("p1", "m1", "p2", "zero")  # their order at the end of a table
+_PROBE_X = {"p1": 1.0, "m1": -1.0, "p2": 2.0, "zero": 0.0}
+
+
+def knn_probe_table(x, n_probes=4, zero_rows=()):
+    """(emb f32 [len(x) + n_probes][16], {probe name: row id}): the rows
+    (x_j, KNN_Y, 0, ...) -- all-zero at the indices zero_rows -- then the first
+    n_probes probe rows."""
+    x = np.asarray(x, np.int64)
+    assert np.abs(x).max(initial=0) <= 20000
+    emb = np.zeros((len(x) + n_probes, KNN_D), np.float32)
+    emb[:len(x), 0] = x
+    emb[:len(x), 1] = KNN_Y
+    emb[list(zero_rows)] = 0.0
+    probes = {}
+    for i, name in enumerate(KNN_PROBES[:n_probes]):
+        emb[len(x) + i, 0] = _PROBE_X[name]
+        probes[name] = len(x) + i
+    emb.setflags(write=False)
+    return emb, probes
+
+
+def knn_select_reference(emb, q, k, eps=1e-16):
+    """(sim f32 [nq][n], w f32 [nq][k], ids i64 [nq][k]) of pinsage_knn_cosine for
+    a table built as above: sim = dot / fl(fl(|q| |e_j|) + eps) in fp32 from exact
+    dots and norms, the k largest by (similarity descending, index ascending)."""
+    emb = np.asarray(emb, np.float32)
+    q = np.asarray(q, np.int64).reshape(-1)
+    n = emb.shape[0]
+    e = emb.astype(np.float64)
+    dots = e[q] @ e.T
+    # the premise: every dot is one integer product below 2^24 (no rounding in
+    # either GEMM arithmetic), and the squared norms are integers a double holds
+    assert ((e[q][:, None, :] * e[None, :, :]) != 0).sum(2).max(initial=0) <= 1
+    assert np.array_equal(dots, np.rint(dots)) and np.abs(dots).max(initial=0) < 2 ** 24
+    sq = (e * e).sum(1)
+    assert np.array_equal(sq, np.rint(sq)) and sq.max() < 2 ** 53
+    norms = np.sqrt(sq).astype(np.float32)
+    den = norms[q][:, None] * norms[None, :] + np.float32(eps)  # two fp32 roundings
+    assert den.dtype == np.float32
+    sim = dots.astype(np.float32) / den + np.float32(0.0)      # -0.0 -> +0.0
+    assert sim.dtype == np.float32 and np.isfinite(sim).all()
+    cols = np.arange(n)
+    order = np.stack([np.lexsort((cols, -s.astype(np.float64)))[:k] for s in sim]).reshape(len(q), k)
+    w = np.take_along_axis(sim, order, 1)
+    return sim, w, order.astype(np.int64)
+
+
+def knn_key_image(sim_row):
+    """f2key (knn.hip): the uint32 whose order is the float's."""
+    u = np.ascontiguousarray(sim_row, np.float32).view(np.uint32)
+    return np.where(u >> 31 != 0, ~u, u | np.uint32(0x80000000)).astype(np.uint32)
+
+
+def knn_select_candidates(sim_row, k):
+    """(key image, candidate mask, candidates per wave) of the kernel's one
+    pass: the threshold is the r-th largest of the row's first KNN_SAMPLE keys."""
+    key = knn_key_image(sim_row)
+    n = len(key)
+    assert 1 <= k <= min(n, KNN_MAX_SORT)
+    S = min(n, KNN_SAMPLE)
+    er = k * S / n
+    r = k if S == n else int(min(S, 1.5 * er + 4.0 * np.sqrt(er) + 8.0))
+    t = np.sort(key[:S])[::-1][r - 1]
+    cand = key >= t
+    j = np.arange(n)
+    n16 = (n // 16) * 16 if n % 4 == 0 else 0
+    wave = np.where(j < n16, (j % (16 * KNN_BLOCK)) // KNN_BLOCK, ((j - n16) % KNN_BLOCK) // 64)
+    return key, cand, np.bincount(wave[cand], minlength=KNN_WAVES)
+
+
+def knn_select_regime(sim_row, k):
+    """The exit knn_select_kernel takes for one row of similarities, replayed:
+    'fast' (one pass, candidates above a sampled threshold), or the whole-row
+    radix select because a wave's segment overflowed ('segment'), fewer than k
+    candidates were found ('few'), or more than KNN_MAX_SORT keys reach the
+    k-th ('ties')."""
+    key, cand, per_wave = knn_select_candidates(sim_row, k)
+    if per_wave.max() > KNN_SEG:
+        return "segment"
+    if per_wave.sum() < k:
+        return "few"
+    kth = np.sort(key[cand])[::-1][k - 1]
+    if int((key >= kth).sum()) > KNN_MAX_SORT:
+        return "ties"
+    return "fast"
+
+
+def check_knn_select(w, ids, ref_w, ref_ids):
+    """Exact: ids equal and values bit for bit.  The first differing (query,
+    column) raises an AssertionError saying whether it is an order swap inside
+    a tie, a missing id, or a value bit."""
+    w = np.ascontiguousarray(w, np.float32)
+    ref_w = np.ascontiguousarray(ref_w, np.float32)
+    ids = np.asarray(ids, np.int64)
+    ref_ids = np.asarray(ref_ids, np.int64)
+    if w.shape != ref_w.shape or ids.shape != ref_ids.shape or w.shape != ids.shape:
+        raise AssertionError(f"knn: shapes {w.shape} / {ids.shape}, reference {ref_w.shape} / {ref_ids.shape}")
+    wb, rb = w.view(np.int32), ref_w.view(np.int32)
+    bad = (ids != ref_ids) | (wb != rb)
+    if not bad.any():
+        return
+    qi, c = (int(v) for v in np.argwhere(bad)[0])
+    where = f"knn query {qi} column {c}: {int(bad.sum())} of {bad.size} entries differ, first here: "
+    got, want = int(ids[qi, c]), int(ref_ids[qi, c])
+    bits = f"value 0x{int(wb[qi, c]) & 0xffffffff:08x} ({w[qi, c]!r}), reference 0x{int(rb[qi, c]) & 0xffffffff:08x} ({ref_w[qi, c]!r})"
+    if got == want:
+        raise AssertionError(where + f"value bit: id {got}, " + bits)
+    if set(ids[qi].tolist()) != set(ref_ids[qi].tolist()):
+        lost = sorted(set(ref_ids[qi].tolist()) - set(ids[qi].tolist()))
+        raise AssertionError(where + f"missing id: got id {got}, reference {want}; "
+                             f"{len(lost)} reference ids absent from the row, first {lost[0]}; " + bits)
+    if wb[qi, c] == rb[qi, c]:
+        raise AssertionError(where + f"order swap inside a tie: got id {got}, reference {want}, both rows "
+                             f"hold the same ids; " + bits)
+    raise AssertionError(where + f"order: got id {got}, reference {want}, the same ids in another order; " + bits)
+
+
+KNN_ATOL = 2e-6  # float tables: the reference's sgemm and the MFMA chain differ in the last bits
+
+
+def knn_sims64(emb, q, idx):
+    e = emb.astype(np.float64)
+    nrm = np.sqrt((e * e).sum(1))
+    a = e[q]
+    b = e[idx]  # [nq, k, d]
+    dot = np.einsum("qd,qkd->qk", a, b)
+    return dot / (nrm[q][:, None] * nrm[idx] + 1e-16)
+
+
+def check_knn_close(w, n, rw, rn, emb, q):
+    """For float tables, whose similarities are not exact: (a) sorted values
+    agree with the reference's within KNN_ATOL, (b) each of our
+    neighbours really has the similarity reported for it, (c) no neighbour twice
+    in a row.  Together: ids differ from the reference only between
+    similarities that tie within the tolerance (including the column the
+    reference drops as 'self', which may be a duplicate row's)."""
+    w, n, rw, rn = (np.asarray(x) for x in (w, n, rw, rn))
+    assert w.shape == rw.shape and n.shape == rn.shape
+    if w.size == 0:
+        return 0.0
+    assert np.abs(w - rw).max() <= KNN_ATOL                         # (a)
+    assert np.abs(knn_sims64(emb, q, n) - w).max() <= KNN_ATOL      # (b)
+    assert (np.diff(w, axis=1) <= 0).all()                           # sorted descending
+    s = np.sort(n, 1)
+    assert (np.diff(s, axis=1) > 0).all()                            # (c)
+    return float((n != rn).mean())
+
+
+def _knn_x_random(nb, seed):
+    rng = np.random.default_rng(seed)
+    return rng.permutation(np.arange(-10000, 9999))[:nb] if nb <= 19999 else rng.integers(-10000, 9999, nb)
+
+
+def _knn_x_desc(nb):
+    return 9998 - np.arange(nb)
+
+
+_KNN_TABLES = {}
+
+
+def knn_select_table(name):
+    """The shared tables of the selection cases, built once (read-only):
+    (emb, probes)."""
+    if name in _KNN_TABLES:
+        return _KNN_TABLES[name]
+    kind, _, arg = name.partition(":")
+    n = int(arg) if arg else 20000
+    n_probes = min(n, 4)
+    nb = n - n_probes
+    zero_rows = ()
+    if kind == "random":
+        x = _knn_x_random(nb, 100 + n)
+    elif kind == "desc":
+        x = _knn_x_desc(nb)
+    elif kind == "block":      # the 600 largest x contiguous in one wave's 1024-block
+        x = _knn_x_random(nb, 3)
+        top = np.argsort(-x, kind="stable")[:600]
+        rest = np.setdiff1d(np.arange(nb), top)
+        dst = np.arange(5120, 5720)
+        out = np.empty_like(x)
+        out[dst] = x[top]
+        out[np.setdiff1d(np.arange(nb), dst)] = x[rest]
+        x = out
+    elif kind == "third":      # every third row the same, largest, value
+        x = np.random.default_rng(4).integers(-10000, 9000, nb)
+        x[::3] = 9000
+    elif kind == "plateau":    # descending with 2500 equal values across the k-th rank
+        x = _knn_x_desc(nb)
+        x[800:3300] = x[800]
+    elif kind == "scattered":  # 300 scattered rows share the value of rank ~900
+        x = _knn_x_random(nb, 5)
+        v = np.sort(x)[::-1][900]
+        at = np.random.default_rng(6).choice(np.flatnonzero(x < v), 300, replace=False)
+        x[at] = v
+    elif kind == "signs":      # mostly negative, 50 positive, three all-zero rows
+        rng = np.random.default_rng(7)
+        x = -rng.integers(1, 20001, nb)
+        at = rng.choice(nb, 53, replace=False)
+        x[at[:50]] = rng.integers(1, 20001, 50)
+        x[at[50:]] = 0
+        zero_rows = tuple(int(i) for i in at[50:])
+    else:
+        raise KeyError(name)
+    _KNN_TABLES[name] = knn_probe_table(x, n_probes, zero_rows)
+    return _KNN_TABLES[name]
+
+
+# (id, table, probe, k, exit): the regime cases.  exit None: whatever the
+# replay reports (the shape cases); a name: the case was built for that exit.
+KNN_REGIME_CASES = (
+    [(f"random-k{k}", "random", "p1", k, "fast") for k in (1, 64, 65, 1000)] + [
+        ("random-k4096", "random", "p1", 4096, "segment"),
+        ("desc-k1000", "desc", "p1", 1000, "few"),
+        ("asc-k1000", "desc", "m1", 1000, "segment"),
+        ("block-k100", "block", "p1", 100, "segment"),
+        ("third-k1000", "third:16384", "p1", 1000, "ties"),
+        # k = 4096 with spare ties: one tie too many would be written past the sort's arrays
+        ("third-k4096", "third:16384", "p1", 4096, "ties"),
+        ("zeroquery-k1000", "random", "zero", 1000, "segment"),
+        ("plateau-k1000", "plateau", "p1", 1000, "few"),
+        ("plateau-k2000", "plateau", "p1", 2000, "segment"),  # the tie cut falls in the second chunk
+        ("scattered-k1000", "scattered", "p1", 1000, "fast"),
+        ("signs-k200", "signs", "p1", 200, "fast"),
+        ("desc20001-k1000", "desc:20001", "p1", 1000, "few"),
+        ("asc20001-k1000", "desc:20001", "m1", 1000, "segment"),
+    ])
+_KNN_SHAPE_EXITS = {(4096, 4096): "segment", (300, 300): "fast", (65, 65): "fast"}
+KNN_SHAPE_CASES = [
+    (f"n{n}-k{k}", f"random:{n}", "p1", k, _KNN_SHAPE_EXITS.get((n, k)))
+    for n in (1, 65, 300, 4096, 4097, 4100, 20001, 20003)
+    for k in sorted({1, min(n, 500)} | ({n} if n <= 4096 else set()))]
+KNN_SELECT_CASES = KNN_REGIME_CASES + KNN_SHAPE_CASES
+
+
+def knn_select_case(case):
+    """(emb, probes, query ids, k, sim, ref_w, ref_ids) of one case; asserts the
+    reference's premise and that the row takes the exit the case names."""
+    _, table, probe, k, want = case
+    emb, probes = knn_select_table(table)
+    q = np.array([probes[probe]], np.int64)
+    sim, ref_w, ref_ids = knn_select_reference(emb, q, k)
+    got = knn_select_regime(sim[0], k)
+    assert want is None or got == want, f"{case[0]}: built for the '{want}' exit, the kernel's logic takes '{got}'"
+    return emb, probes, q, k, sim, ref_w, ref_ids

@@ -10,18 +10,20 @@ checks (a) the sorted top-k similarity values agree within 2e-6 absolute
 (|cos| <= 1), (b) every returned neighbour's fp64 similarity matches the value
 reported for it within 2e-6, and (c) no neighbour appears twice: neighbour ids
 then differ from the reference's only among similarities that tie within the
-tolerance.  Exact ties (duplicate rows) keep the lower index here; torch's
-CPU topk orders them by libstdc++'s selection, which is not replayed for kNN.
+tolerance (parity_util.check_knn_close).  Exact ties (duplicate rows) keep the
+lower index here; torch's CPU topk orders them by libstdc++'s selection, which
+is not replayed.  The documented rule itself (similarity descending, then index
+ascending) and every exit of the selection kernel are checked id for id and bit
+for bit in tests/test_gpu_knn_select.py, on tables whose similarities are exact.
 """
 import numpy as np
 import pytest
 import torch
 
 from conftest import golden
+from parity_util import check_knn_close as _check_knn
 
 pytestmark = pytest.mark.gpu
-
-ATOL = 2e-6
 
 
 @pytest.fixture(autouse=True)
@@ -55,33 +57,6 @@ def test_ppr_knn_bit_exact(gname):
         assert (tk.values.numpy() == d[f"val_{k}"]).all(), k
         assert (tk.indices.numpy() == d[f"idx_{k}"]).all(), k
         assert _after_ok(d[f"after_{k}"]), k
-
-
-def _sims64(emb, q, idx):
-    e = emb.astype(np.float64)
-    nrm = np.sqrt((e * e).sum(1))
-    a = e[q]
-    b = e[idx]  # [nq, k, d]
-    dot = np.einsum("qd,qkd->qk", a, b)
-    return dot / (nrm[q][:, None] * nrm[idx] + 1e-16)
-
-
-def _check_knn(w, n, rw, rn, emb, q):
-    """(a) sorted values agree with the reference's within ATOL, (b) each of our
-    neighbours really has the similarity reported for it, (c) no neighbour twice
-    in a row.  Together: ids differ from the reference only between
-    similarities that tie within the tolerance (including the column the
-    reference drops as 'self', which may be a duplicate row's)."""
-    w, n, rw, rn = (np.asarray(x) for x in (w, n, rw, rn))
-    assert w.shape == rw.shape and n.shape == rn.shape
-    if w.size == 0:
-        return 0.0
-    assert np.abs(w - rw).max() <= ATOL                             # (a)
-    assert np.abs(_sims64(emb, q, n) - w).max() <= ATOL              # (b)
-    assert (np.diff(w, axis=1) <= 0).all()                           # sorted descending
-    s = np.sort(n, 1)
-    assert (np.diff(s, axis=1) > 0).all()                            # (c)
-    return float((n != rn).mean())
 
 
 @pytest.mark.parametrize("k", [50, 1000])

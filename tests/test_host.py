@@ -471,6 +471,84 @@ def test_frontier_plan_checker_rejects_single_defects():
         check_frontier_plan(got, absent)
 
 
+def test_knn_select_cases_reach_their_regimes_and_checker_rejects_defects():
+    """Every case of tests/test_gpu_knn_select.py, on the host: the table meets
+    the exact reference's premise and the replay of knn_select_kernel's decision
+    (parity_util.knn_select_regime) takes the exit the case was built for; all
+    four exits are reached.  Then parity_util.check_knn_select passes a correct
+    answer and names each single defect of one."""
+    import parity_util as pu
+    exits = set()
+    for case in pu.KNN_SELECT_CASES:
+        emb, probes, q, k, sim, ref_w, ref_ids = pu.knn_select_case(case)  # asserts premise and exit
+        exits.add(pu.knn_select_regime(sim[0], k))
+        assert ref_w.shape == (1, k) and (np.diff(ref_w[0]) <= 0).all(), case[0]
+        assert len(set(ref_ids[0].tolist())) == k, case[0]
+    assert exits == {"fast", "few", "segment", "ties"}
+    # what the cases say they pin, read off the reference
+    _, _, _, _, sim, w, ids = pu.knn_select_case(next(c for c in pu.KNN_SELECT_CASES if c[0] == "zeroquery-k1000"))
+    assert ids[0].tolist() == list(range(1000)) and not w.view(np.int32).any()   # an n-way tie at +0.0
+    emb, probes, _, _, sim, w, ids = pu.knn_select_case(
+        next(c for c in pu.KNN_SELECT_CASES if c[0] == "third-k1000"))
+    assert ids[0, :2].tolist() == [probes["p1"], probes["p2"]]                   # both are exactly 1.0
+    assert ids[0, 2:].tolist() == list(range(0, 3 * 998, 3))                      # the lowest multiples of 3
+    assert int((sim[0] == w[0, -1]).sum()) > pu.KNN_MAX_SORT
+    emb, probes, _, _, sim, w, ids = pu.knn_select_case(
+        next(c for c in pu.KNN_SELECT_CASES if c[0] == "signs-k200"))
+    assert (w[0] > 0).any() and (w[0] == 0).sum() >= 4 and (w[0] < 0).any()
+    _, _, _, k, sim, _, _ = pu.knn_select_case(next(c for c in pu.KNN_SELECT_CASES if c[0] == "block-k100"))
+    _, _, per_wave = pu.knn_select_candidates(sim[0], k)
+    assert (per_wave > pu.KNN_SEG).sum() == 1 and per_wave[5] > pu.KNN_SEG     # columns 5120 .. 6143: wave 5
+    assert per_wave.sum() < 2 * pu.KNN_SEG                                     # one full segment, not a full row
+    # (2, 0, ...) gives the values of (1, 0, ...) bitwise; (-1, 0, ...) the reverse order
+    emb, probes = pu.knn_select_table("desc")
+    sim, w, ids = pu.knn_select_reference(emb, [probes["p1"], probes["p2"], probes["m1"]], 1000)
+    assert np.array_equal(sim[0].view(np.int32), sim[1].view(np.int32))
+    assert np.array_equal(sim[2], -sim[0] + np.float32(0.0))
+    assert pu.knn_select_regime(sim[2], 1000) == "segment"
+
+    # the checker: a case whose k-th value is tied (300 rows share it)
+    _, _, q, k, sim, w, ids = pu.knn_select_case(
+        next(c for c in pu.KNN_SELECT_CASES if c[0] == "scattered-k1000"))
+    pu.check_knn_select(w.copy(), ids.copy(), w, ids)
+    _, w1, ids1 = pu.knn_select_reference(pu.knn_select_table("scattered")[0], q, k + 1)
+    wb = w.view(np.int32)[0]
+    tie = int(np.flatnonzero(wb[1:] == wb[:-1])[0])           # columns tie, tie + 1 hold one value
+    assert wb[k - 1] == w1.view(np.int32)[0, k]               # and the k-th ties with the (k+1)-th
+    plain = int(np.flatnonzero(wb[1:] != wb[:-1])[5])         # columns plain, plain + 1 differ
+
+    def defect(change, match):
+        gw, gi = w.copy(), ids.copy()
+        change(gw, gi)
+        with pytest.raises(AssertionError, match=match):
+            pu.check_knn_select(gw, gi, w, ids)
+
+    def tie_swapped(gw, gi):
+        gi[0, [tie, tie + 1]] = gi[0, [tie + 1, tie]]
+
+    def kth_replaced(gw, gi):
+        gw[0, k - 1], gi[0, k - 1] = w1[0, k], ids1[0, k]
+
+    def one_ulp(gw, gi):
+        gw.view(np.int32)[0, 17] += 1
+
+    def columns_exchanged(gw, gi):
+        gi[0, [plain, plain + 1]] = gi[0, [plain + 1, plain]]
+        gw[0, [plain, plain + 1]] = gw[0, [plain + 1, plain]]
+
+    defect(tie_swapped, rf"^knn query 0 column {tie}: 2 of {k} entries differ, first here: order swap inside a tie")
+    defect(kth_replaced, rf"^knn query 0 column {k - 1}: 1 of {k} entries differ, first here: missing id")
+    defect(one_ulp, rf"^knn query 0 column 17: 1 of {k} entries differ, first here: value bit")
+    defect(columns_exchanged, rf"^knn query 0 column {plain}: 2 of {k} entries differ, first here: order: ")
+    with pytest.raises(AssertionError, match="^knn: shapes"):
+        pu.check_knn_select(w[:, :-1], ids[:, :-1], w, ids)
+    # the reference refuses a table outside its premise (a dot of two terms)
+    bad = np.array(pu.knn_select_table("random:65")[0])
+    bad[3, 0], bad[3, 1] = 1.0, 1.0
+    with pytest.raises(AssertionError):
+        pu.knn_select_reference(bad, [3], 5)
+
+
 def test_bench_refuses_a_world_size_other_than_gpus():
     """bench.py started by a launcher with WORLD_SIZE != --gpus exits non-zero
     before touching the GPU (launch_ranks)."""
