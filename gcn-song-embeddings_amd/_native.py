@@ -47,6 +47,13 @@ class EnginePlanOffsets(ctypes.Structure):
                 ("rank_off", i64), ("pos_sorted", i64)]
 
 
+class EngineHeadOffsets(ctypes.Structure):
+    """pinsage_engine_head_offsets_t: where a workspace keeps the head's
+    activations and the loss's accumulators (read back by the tests)."""
+    _fields_ = [("H1", i64), ("dP1", i64), ("dp_top", i64), ("nrm_top", i64), ("G", i64), ("Kc", i64),
+                ("Gp", i64), ("cap", i64)]
+
+
 # name -> (restype, argtypes)
 _SIGS = {
     "pinsage_version": (ctypes.c_int, []),
@@ -143,6 +150,7 @@ _SIGS = {
     "pinsage_engine_num_params": (i64, [vp]),
     "pinsage_engine_offsets": (ctypes.c_int, [vp, ctypes.POINTER(EngineOffsets)]),
     "pinsage_engine_plan_offsets": (ctypes.c_int, [vp, ctypes.POINTER(EnginePlanOffsets)]),
+    "pinsage_engine_head_offsets": (ctypes.c_int, [vp, ctypes.POINTER(EngineHeadOffsets)]),
     "pinsage_engine_set_tensors": (ctypes.c_int, [vp, vp, i64, vp, vp, i64, vp, vp, vp, vp]),
     "pinsage_engine_set_feature_planes": (ctypes.c_int, [vp, vp, i64]),
     "pinsage_engine_set_frontier_fork": (ctypes.c_int, [vp, ctypes.c_int]),

@@ -2116,7 +2116,7 @@ int launch_loss(const float* Z, int d, const int32_t* pos_rank, int B, float mar
   // G and Kc are zero on entry (init_workspace; then the head backward (or
   // dz_combine) and the first backward kernel leave them zero)
   PS_REQUIRE(d <= 256, kErrArg, "loss: out_dim must be <= 256");
-  PS_REQUIRE(d <= 1024 && 1024 % d == 0, kErrArg, "loss: out_dim must divide 1024");
+  PS_REQUIRE(d <= 1024 && 1024 % d == 0, kErrArg, "loss: needs an out_dim that divides 1024");
   const int nblk = ceil_div(B, 4);
   // (features past 64 FPL per lane are streamed after the row stores, one
   // waited round trip per 64 columns: C2's 1024 take 16 per lane instead)

@@ -1514,6 +1514,25 @@ int pinsage_engine_plan_offsets(const pinsage_engine* e, pinsage_engine_plan_off
   return kOk;
 }
 
+int pinsage_engine_head_offsets(const pinsage_engine* e, pinsage_engine_head_offsets_t* o) {
+  if (!e || !o) {
+    set_error("engine_head_offsets: null argument");
+    return kErrArg;
+  }
+  const Engine* E = reinterpret_cast<const Engine*>(e);
+  const LayerBuf& top = E->L.back();
+  *o = pinsage_engine_head_offsets_t{};
+  o->H1 = (int64_t)E->H1;
+  o->dP1 = (int64_t)E->dP1;
+  o->dp_top = (int64_t)top.dp;
+  o->nrm_top = (int64_t)top.nrm;
+  o->G = (int64_t)E->G;
+  o->Kc = (int64_t)E->Kc;
+  o->Gp = (int64_t)E->Gp;
+  o->cap = top.S.cap;
+  return kOk;
+}
+
 int pinsage_engine_timing(pinsage_engine* e, int enable) {
   Engine* E = reinterpret_cast<Engine*>(e);
   for (auto& t : E->sites)

@@ -239,6 +239,24 @@ typedef struct {
   int64_t rank_off, pos_sorted;
 } pinsage_engine_plan_offsets_t;
 int pinsage_engine_plan_offsets(const pinsage_engine* e, pinsage_engine_plan_offsets_t* out);
+/* The head's and the loss's buffers, for tests that read them back (and write
+ * Z or garbage into Gp before a loss): workspace byte offsets, rows = |S_top|
+ * live rows (count_S of the top layer), out = the configuration's out_dim:
+ *   H1      f32 [rows][out]     lrelu(y G1^T + b1)
+ *   dP1     f32 [rows][out]     (dZ G2) * lrelu'(H1)
+ *   dp_top  f32 [rows][out]     the top conv layer's dp (pre-activation gradient)
+ *   nrm_top f32 [rows]          the top conv layer's row norms ||lrelu(.)||
+ *   G       f32 [3][cap][out]   per call (query / positive / negative) and rank, the
+ *                               summed loss cotangent of the rank's positions
+ *   Kc      i32 [3][cap]        per call and rank, the number of positions
+ *   Gp      f32 [max_pos][out]  a repeated rank's cotangent rows by position
+ *   cap     the top set's capacity: the row stride of G and Kc (not an offset)
+ * G and Kc are zero over their whole capacity outside a loss .. backward pair.
+ * A struct of its own, as pinsage_engine_plan_offsets_t. */
+typedef struct {
+  int64_t H1, dP1, dp_top, nrm_top, G, Kc, Gp, cap;
+} pinsage_engine_head_offsets_t;
+int pinsage_engine_head_offsets(const pinsage_engine* e, pinsage_engine_head_offsets_t* out);
 /* General form of the same GEMM, for per-configuration tests and
  * microbenchmarks: C = op(A) op(B) with A K-major ([M][K], rows gathered by
  * a_idx) or M-major ([K][M], k-rows gathered), B K-major ([N][K]) or N-major
@@ -613,7 +631,13 @@ int pinsage_engine_gather_output(pinsage_engine* e, void* ws, int64_t n_ids, flo
  * The monitor kernel (loss / node-feature loss / variance scalars, on an engine
  * side stream, dependent on this loss) is enqueued by the next engine call
  * that enqueues work (normally the backward, right behind its first kernel;
- * PINSAGE_DEFER_SIDE=0/1 enqueues it here) and joined at the backward's end. */
+ * PINSAGE_DEFER_SIDE=0/1 enqueues it here) and joined at the backward's end.
+ * The loss kernels need an out_dim that divides 1024 (4, 8, 16, 32, 64, 128 of
+ * the widths pinsage_engine_create accepts: the monitor kernel deals 1024
+ * threads over whole rows).  Any other width (12, 96, 100, ...) is refused with
+ * PINSAGE_ERR_ARG ("needs an out_dim that divides 1024") before anything is launched;
+ * such an engine still serves forwards, pinsage_engine_set_output_grad and
+ * the backward. */
 int pinsage_engine_loss(pinsage_engine* e, void* ws, int64_t batch_size, float margin,
                         int with_monitors, void* stream);
 /* dZ from an upstream gradient of gather_output (single call, autograd path) */

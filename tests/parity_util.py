@@ -623,3 +623,431 @@ def knn_select_case(case):
     got = knn_select_regime(sim[0], k)
     assert want is None or got == want, f"{case[0]}: built for the '{want}' exit, the kernel's logic takes '{got}'"
     return emb, probes, q, k, sim, ref_w, ref_ids
+
+
+# ----------------------------------------------------------------------------- small tables
+def perm_table(n, T, ld, seed, device="cuda"):
+    """small universes: nb[i][t] = (p[i] + t) % n over a random permutation p
+    (every column is a permutation: a frontier over all rows is the universe);
+    wn: random 32-bit patterns (int32; the engine copies them as they are)"""
+    assert T <= n
+    rng = np.random.default_rng(seed)
+    p = rng.permutation(n)
+    nb = (p[:, None] + np.arange(ld)[None, :]) % n
+    wb = rng.integers(0, 1 << 32, (n, ld), dtype=np.uint64).astype(np.uint32).view(np.int32)
+    return torch.from_numpy(nb.astype(np.int32)).to(device), torch.from_numpy(wb).to(device)
+
+
+# ----------------------------------------------------------------------------- loss and head
+# The end of the train step (tests/test_gpu_head_loss.py): the loss kernels of
+# conv.hip (loss_triple_kernel, det_put, rep_sum_kernel, loss_monitor_kernel,
+# dout_accum_kernel, dz_scale_kernel), the head kernels of head.hip and the
+# head inside the top layer's tile (aggw.hip), each against float64 numpy that
+# reads only the inputs of the stage it checks.  tests/test_host.py pins the
+# loss reference to torch autograd of max_margin_loss, checks that every case
+# of the table has the multiplicities it claims and a hinge argument away from
+# zero, and that each checker rejects a single planted defect.
+U24 = 2.0 ** -24          # fp32 unit roundoff
+HL_N, HL_T = 300, 3       # universe and neighbourhood size of every case
+SLOPE = 0.01              # leaky_relu's negative slope (kSlope, common.h)
+HINGE_ATOL = 1e-5         # the hinge argument's own fp32 error (this module's part 3)
+COT_RTOL = 1e-5           # cotangent rows (test_triplet_loss_kernel_matches_torch)
+ARG_MIN = 1e-4            # every case: |hinge argument| >= this, planted ties apart
+
+
+def _normalize64(x):
+    return x / np.maximum(np.linalg.norm(x, axis=1, keepdims=True), 1e-12)
+
+
+def loss_reference(Z_by_rank, pos_rank, B, margin, feats=None, batch=None):
+    """max_margin_loss over the batch positions p = 3 b + c (c = query /
+    positive / negative) whose output row is Z_by_rank[pos_rank[p]], in float64:
+
+      arg [B]        cos(q, n) - cos(q, p) + margin, rows normalised with
+                     max(|x|, 1e-12) as F.normalize does
+      active [B]     arg >= 0 (a tie is active: the kernel's rule, and what
+                     clamp(min=0)'s backward gives)
+      loss           mean of the active arguments
+      cot [3B][d]    d loss / d (the un-normalised row of position p); zero
+                     rows for inactive triples
+      cot_scale [3B] |g_hat| / |x|: cot = (g_hat - x_hat (x_hat . g_hat)) / |x| is a
+                     difference of two vectors no longer than the gradient g_hat
+                     of the normalised row, so its fp32 rounding is relative to
+                     that length, not to the difference (all ids equal: cot = 0)
+      K [3][R]       number of positions of call c with rank r
+      Gsum [3][R][d] sum of cot over those positions; Gscale, Gterms [3][R]: the
+                     sums of cot_scale and of |cot| rows over them
+      dZ [R][d]      sum_c K[c][r] Gsum[c][r] (put_embeddings' index_put backward
+                     hands every position of a repeated id the sum)
+      nfl, var       oracle.triplet_monitors' formulas; sumsq = sum |h_q|^2 over
+                     the raw query rows (feats / batch None: nfl = None)"""
+    Z = np.asarray(Z_by_rank, np.float64)
+    pr = np.asarray(pos_rank, np.int64).reshape(B, 3)
+    R, d = Z.shape
+    x = Z[pr]                                              # [B][3][d]
+    nrm = np.maximum(np.linalg.norm(x, axis=2), 1e-12)     # [B][3]
+    h = x / nrm[:, :, None]
+    arg = (h[:, 0] * h[:, 2]).sum(1) - (h[:, 0] * h[:, 1]).sum(1) + margin
+    active = arg >= 0
+    g = np.where(active, 1.0 / B, 0.0)[:, None]
+    ghat = np.stack([g * (h[:, 2] - h[:, 1]), -g * h[:, 0], g * h[:, 0]], 1)
+    cot = (ghat - h * (h * ghat).sum(2, keepdims=True)) / nrm[:, :, None]
+    cot_scale = np.linalg.norm(ghat, axis=2) / nrm
+    K = np.zeros((3, R), np.int64)
+    Gsum = np.zeros((3, R, d))
+    Gscale = np.zeros((3, R))
+    Gterms = np.zeros((3, R))
+    for c in range(3):
+        np.add.at(K[c], pr[:, c], 1)
+        np.add.at(Gsum[c], pr[:, c], cot[:, c])
+        np.add.at(Gscale[c], pr[:, c], cot_scale[:, c])
+        np.add.at(Gterms[c], pr[:, c], np.linalg.norm(cot[:, c], axis=1))
+    hq = x[:, 0]
+    out = dict(arg=arg, active=active, loss=float(np.where(active, arg, 0.0).sum() / B),
+               cot=cot.reshape(3 * B, d), cot_scale=cot_scale.reshape(3 * B), K=K, Gsum=Gsum, Gscale=Gscale,
+               Gterms=Gterms, dZ=(K[:, :, None] * Gsum).sum(0), sumsq=float((hq * hq).sum()),
+               var=float(((hq - hq.mean(0)) ** 2).sum() / (B - 1)), mean_sq=float((hq.mean(0) ** 2).sum()),
+               nfl=None, pos_rank=pr.reshape(-1), B=B)
+    if feats is not None:
+        f = np.asarray(feats, np.float64)[np.asarray(batch, np.int64).reshape(B, 3)]
+        fq, fp, fn = (_normalize64(f[:, c]) for c in range(3))
+
+        def cos(a, b):  # F.cosine_similarity, eps 1e-8
+            return (a * b).sum(1) / np.maximum(np.linalg.norm(a, axis=1) * np.linalg.norm(b, axis=1), 1e-8)
+        out["nfl"] = float(np.maximum((1 - cos(fq, fp)) - (1 - cos(fq, fn)) + 1e-4, 0.0).mean())
+    return out
+
+
+def hinge_replay32(Z_by_rank, pos_rank, B, margin):
+    """the hinge argument in float32 arithmetic (numpy), for the planted ties:
+    p == n gives the same products in the same order, so exactly 0 at margin 0"""
+    Z = np.asarray(Z_by_rank, np.float32)
+    x = Z[np.asarray(pos_rank, np.int64).reshape(B, 3)]
+    nrm = np.maximum(np.sqrt((x * x).sum(2, dtype=np.float32)), np.float32(1e-12))
+    cqp = (x[:, 0] * x[:, 1]).sum(1, dtype=np.float32) / (nrm[:, 0] * nrm[:, 1])
+    cqn = (x[:, 0] * x[:, 2]).sum(1, dtype=np.float32) / (nrm[:, 0] * nrm[:, 2])
+    return cqn - cqp + np.float32(margin)
+
+
+def _first_bad(name, err, bound, labels):
+    """raise naming the first entry with not (err <= bound) (a NaN is wrong);
+    labels(flat index tuple) -> text.  Returns the largest err / bound."""
+    err, bound = np.asarray(err, np.float64), np.asarray(bound, np.float64)
+    ok = err <= bound
+    if not ok.all():
+        idx = tuple(int(v) for v in np.argwhere(~ok)[0])
+        raise AssertionError(f"{name}: {int((~ok).sum())} of {ok.size} entries outside their bound, first at "
+                             f"{labels(idx)}: error {err[idx]:.3e}, bound {bound[idx]:.3e}")
+    with np.errstate(divide="ignore", invalid="ignore"):
+        ratio = np.where(bound > 0, err / np.where(bound > 0, bound, 1.0), 0.0)
+    return float(ratio.max()) if ratio.size else 0.0
+
+
+def _exact(name, got, want, labels):
+    got, want = np.asarray(got), np.asarray(want)
+    if got.shape != want.shape:
+        raise AssertionError(f"{name}: shape {got.shape}, reference {want.shape}")
+    bad = np.argwhere(~(got == want))
+    if len(bad):
+        idx = tuple(int(v) for v in bad[0])
+        raise AssertionError(f"{name}: {len(bad)} of {want.size} entries differ, first at {labels(idx)}: "
+                             f"got {got[idx]!r}, reference {want[idx]!r}")
+
+
+CALLS = ("query", "positive", "negative")
+
+
+def check_loss(got, ref, mode, with_feats=True, scalars=True):
+    """The loss kernels' outputs against loss_reference.  got: hinge [B], G
+    [3][cap][d], Kc [3][cap], Gp [3B][d] (None in the atomics regime), scal [4]
+    = {loss, nfl, sum |h_q|^2, variance}.  mode: 'head' (the default engine:
+    a repeated rank's rows stay in Gp for the head backward, G holds the
+    single-position ranks only), 'rep_sum' (G also holds the repeated ranks'
+    sums), 'atomic' (no position CSR: G holds float-atomic sums, no Gp).
+
+    Bounds: hinge HINGE_ATOL absolute, a reference argument of exactly 0 (a
+    planted tie) exactly 0.0 and active; the active set equal for every triple;
+    Kc exact over the whole capacity; a cotangent row within COT_RTOL of
+    max(|row|, cot_scale) (loss_reference), a sum of n rows within the sum of
+    its rows' bounds plus (n - 1) 2^-24 sum |row| for its n - 1 fp32 additions
+    in any order; G zero wherever no position lands (rows past the top set
+    too); loss 1e-6 relative + 1e-9, nfl 1e-4 relative, sum |h_q|^2 (B d + 4)
+    2^-24 relative (non-negative terms), variance 1e-5 relative plus the floor
+    a rounded mean leaves when the query rows (nearly) coincide: deviations
+    from m (1 + e) instead of m add B m^2 e^2 to the sum of squares (the first
+    order term cancels, sum (h - m) = 0), |e| <= (B / 4 + 8) 2^-24 for the
+    additions of the block sums and their merge -- B / (B - 1) |mean|^2 e^2,
+    1e-11 of |mean|^2 at B = 75 and nothing beside 1e-5 of a Gaussian batch's
+    variance.
+    Returns the largest error / bound of the cotangent rows."""
+    B, pr = ref["B"], ref["pos_rank"]
+    R, d = ref["Gsum"].shape[1:]
+    hinge = np.asarray(got["hinge"], np.float64)
+    tri = lambda i: f"triple {i[0]}"
+    _first_bad("hinge", np.abs(hinge - ref["arg"]), np.full(B, HINGE_ATOL), tri)
+    ties = ref["arg"] == 0.0
+    _exact("hinge of the planted ties", hinge[ties], np.zeros(int(ties.sum())), lambda i: f"tie {i[0]}")
+    _exact("active set (hinge >= 0)", hinge >= 0, ref["active"], tri)
+    Kc = np.asarray(got["Kc"], np.int64)
+    Kref = np.zeros_like(Kc)
+    Kref[:, :R] = ref["K"]
+    _exact("Kc", Kc, Kref, lambda i: f"call {CALLS[i[0]]}, rank {i[1]}")
+    G = np.asarray(got["G"], np.float64)
+    single = ref["K"].sum(0) == 1                      # ranks with one position over all calls
+    in_G = np.ones((3, R), bool) if mode != "head" else np.broadcast_to(single, (3, R))
+    Gref = np.where(in_G[:, :, None], ref["Gsum"], 0.0)
+    bound = np.where(in_G, COT_RTOL * np.maximum(ref["Gscale"], np.linalg.norm(ref["Gsum"], axis=2)) +
+                     np.maximum(ref["K"] - 1, 0) * U24 * ref["Gterms"], 0.0)
+    err = np.linalg.norm(G[:, :R] - Gref, axis=2)
+    err = np.where(np.isnan(err), np.inf, err)
+    worst = _first_bad("G", err, bound, lambda i: f"call {CALLS[i[0]]}, rank {i[1]}")
+    _exact("G past the top set", G[:, R:] == 0, np.ones_like(G[:, R:], bool),
+           lambda i: f"call {CALLS[i[0]]}, row {R + i[1]}, column {i[2]}")
+    if mode != "atomic":
+        Gp = np.asarray(got["Gp"], np.float64)
+        rep = ~single[pr]                              # positions of repeated ranks
+        e = np.linalg.norm(Gp - ref["cot"], axis=1)
+        e = np.where(rep, np.where(np.isnan(e), np.inf, e), 0.0)
+        b = COT_RTOL * np.maximum(ref["cot_scale"], np.linalg.norm(ref["cot"], axis=1))
+        worst = max(worst, _first_bad("Gp", e, b, lambda i: f"position {i[0]} (triple {i[0] // 3}, call "
+                                      f"{CALLS[i[0] % 3]}, rank {pr[i[0]]})"))
+        zero_rows = rep & ~np.repeat(ref["active"], 3)
+        _exact("Gp rows of inactive triples", Gp[zero_rows] == 0, np.ones((int(zero_rows.sum()), d), bool),
+               lambda i: f"position {np.flatnonzero(zero_rows)[i[0]]}, column {i[1]}")
+    if not scalars:  # (the monitors have not run yet)
+        return worst
+    scal = np.asarray(got["scal"], np.float64)
+    for k, (name, want, tol) in enumerate((("loss", ref["loss"], 1e-6), ("nfl", ref["nfl"], 1e-4),
+                                           ("sum |h_q|^2", ref["sumsq"], (B * d + 4) * U24),
+                                           ("variance", ref["var"], 1e-5))):
+        if name == "nfl" and not with_feats:
+            want, tol = 0.0, 0.0                       # no feature monitor: the scalar is 0
+        floor = {"loss": 1e-9, "variance": B / (B - 1) * ref["mean_sq"] * ((B / 4 + 8) * U24) ** 2}.get(name, 0.0)
+        if not abs(scal[k] - want) <= tol * abs(want) + floor:
+            raise AssertionError(f"scalar {k} ({name}): got {scal[k]!r}, reference {want!r}, relative bound {tol:.3e}")
+    return worst
+
+
+def rep_sum32(Gp, pos_rank, R, n_groups=3):
+    """rep_sum_kernel's additions in numpy float32: for every rank with >= 2
+    positions, G[p % n_groups][r] = the float32 sum from zero, in increasing
+    position order, of the rank's Gp rows; None where it writes nothing"""
+    Gp = np.asarray(Gp, np.float32)
+    pr = np.asarray(pos_rank, np.int64)
+    out = {}
+    for r in np.flatnonzero(np.bincount(pr, minlength=R) >= 2):
+        for p in np.flatnonzero(pr == r):
+            key = (int(p % n_groups), int(r))
+            out[key] = out.get(key, np.zeros(Gp.shape[1], np.float32)) + Gp[p]
+    return out
+
+
+def check_rep_sum_exact(G, Gp, pos_rank, R, n_groups=3):
+    """PINSAGE_HEAD_REP_SUM=0 (and the autograd path, one group): a repeated
+    rank's G rows are, bit for bit, rep_sum32 of its Gp rows; its groups
+    without a position hold zeros"""
+    G = np.asarray(G, np.float32)
+    want = rep_sum32(Gp, pos_rank, R, n_groups)
+    pr = np.asarray(pos_rank, np.int64)
+    for r in np.flatnonzero(np.bincount(pr, minlength=R) >= 2):
+        for c in range(n_groups):
+            w = want.get((c, int(r)), np.zeros(G.shape[2], np.float32))
+            bad = np.flatnonzero(G[c, r].view(np.uint32) != w.view(np.uint32))
+            if len(bad):
+                raise AssertionError(f"rep_sum: call {CALLS[c]}, rank {r} ({int((pr == r).sum())} positions), column "
+                                     f"{bad[0]}: got {G[c, r, bad[0]]!r}, the ordered float32 sum is {w[bad[0]]!r}")
+
+
+def dz_reference(G, Kc, Gp, pos_rank, R, mode, n_groups=3):
+    """dZ[r] = sum_c K[c][r] Gsum[c][r] in float64 from the device's own G / Kc /
+    Gp (mode as check_loss: 'head' sums a repeated rank's Gp rows by group p %
+    n_groups), and the bound of its fp32 evaluation: (n + 4) 2^-24 sum |terms|
+    with n = the rank's positions (their additions) + n_groups (the products
+    and the additions over calls)"""
+    G, Gp = np.asarray(G, np.float64), (None if Gp is None else np.asarray(Gp, np.float64))
+    K = np.asarray(Kc, np.int64)[:, :R]
+    pr = np.asarray(pos_rank, np.int64)
+    Gs, Ga = G[:, :R].copy(), np.abs(G[:, :R])
+    cnt = np.bincount(pr, minlength=R)
+    if mode == "head":
+        for r in np.flatnonzero(cnt >= 2):
+            Gs[:, r], Ga[:, r] = 0.0, 0.0
+            for p in np.flatnonzero(pr == r):
+                Gs[p % n_groups, r] += Gp[p]
+                Ga[p % n_groups, r] += np.abs(Gp[p])
+    dz = (K[:n_groups, :, None] * Gs[:n_groups]).sum(0)
+    mag = (K[:n_groups, :, None] * Ga[:n_groups]).sum(0)
+    return dz, (cnt[:, None] + n_groups + 4) * U24 * mag
+
+
+def check_rows(name, got_full, R, ref, bound, sentinel=None):
+    """got_full [cap][o] against ref [R][o] within bound, entry by entry, naming
+    the first wrong (row, column); rows R .. cap - 1 must still hold the
+    sentinel bits the test wrote there (a store past the live rows -- a column
+    past o of the last row lands there -- shows).  Returns max error / bound."""
+    got_full = np.asarray(got_full)
+    got = got_full[:R].astype(np.float64)
+    err = np.abs(got - ref)
+    err = np.where(np.isnan(err), np.inf, err)
+    worst = _first_bad(name, err, bound, lambda i: f"row {i[0]}, column {i[1]}")
+    if sentinel is not None and got_full.shape[0] > R:
+        tail = got_full[R:].astype(np.float32).view(np.uint32)
+        _exact(f"{name} past its {R} live rows", tail, np.full_like(tail, sentinel),
+               lambda i: f"row {R + i[0]}, column {i[1]}")
+    return worst
+
+
+def gemm_bound(n, absterms):
+    """|fl(sum_k a_k b_k) - sum_k a_k b_k| <= (n + 4) 2^-24 sum_k |a_k b_k| for n
+    terms: each product is rounded once (relative error <= u = 2^-24) or fused
+    into the running sum (no rounding of its own), and a sum of n numbers in
+    any order (sequential, pairwise, MFMA chains combined afterwards) passes
+    each term through at most n - 1 additions, each with relative error <= u:
+    (1 + u)^n - 1 <= n u / (1 - n u); the + 4 absorbs the second-order term
+    for the n used here (n u < 1e-4), a bias added after the sum and the
+    final conversion.  absterms = |A| @ |B| (+ |bias|)."""
+    return (n + 4) * U24 * np.asarray(absterms, np.float64)
+
+
+def lrelu64(x):
+    return np.where(x > 0, x, SLOPE * x)
+
+
+def lrelu_grad64(y):
+    return np.where(y > 0, 1.0, SLOPE)
+
+
+def head_reference_fwd(y, G1w, G1b, G2w, H1_gpu):
+    """H1 = lrelu(y G1^T + b1) from the device's y, Z = H1 G2^T from the device's
+    H1; each with its bound (lrelu is 1-Lipschitz: the product's bound holds
+    behind it)"""
+    y, G1w, G1b, G2w, H1g = (np.asarray(a, np.float64) for a in (y, G1w, G1b, G2w, H1_gpu))
+    o = G1w.shape[0]
+    H1 = lrelu64(y @ G1w.T + G1b)
+    return dict(H1=H1, H1_bound=gemm_bound(o + 1, np.abs(y) @ np.abs(G1w.T) + np.abs(G1b)),
+                Z=H1g @ G2w.T, Z_bound=gemm_bound(o, np.abs(H1g) @ np.abs(G2w.T)))
+
+
+def head_reference_bwd(dZ, H1, y, nrm, G1w, G2w, dP1_gpu):
+    """The head backward, each step from the device's own inputs to that step:
+    dP1 = (dZ G2) lrelu'(H1); dY = dP1 G1 from the device's dP1; dp = lrelu'(y)
+    (dY - y (y . dY)) / nrm; dG2 = dZ^T H1, dG1 = dP1^T y, db1 = sum_rows dP1.
+    dp's bound carries dY's (E) through the dot product (sum |y| E + the dot's
+    own (o + 4) u sum |y dY|), the subtraction, and the three roundings of the
+    scaling: (E + |y| E_dot + 4 u (|dY| + |y| |dot|)) lrelu' / nrm."""
+    dZ, H1, y, nrm, G1w, G2w, dP1g = (np.asarray(a, np.float64) for a in (dZ, H1, y, nrm, G1w, G2w, dP1_gpu))
+    R, o = dZ.shape
+    s = lrelu_grad64(H1)
+    out = dict(dP1=(dZ @ G2w) * s, dP1_bound=gemm_bound(o, np.abs(dZ) @ np.abs(G2w)) * s)
+    dY = dP1g @ G1w
+    E = gemm_bound(o, np.abs(dP1g) @ np.abs(G1w))
+    dot = (y * dY).sum(1, keepdims=True)
+    E_dot = (np.abs(y) * E).sum(1, keepdims=True) + gemm_bound(o, (np.abs(y * dY)).sum(1, keepdims=True))
+    sy = lrelu_grad64(y)
+    out["dp"] = sy * (dY - y * dot) / nrm[:, None]
+    out["dp_bound"] = sy * (E + np.abs(y) * E_dot + 4 * U24 * (np.abs(dY) + np.abs(y * dot))) / nrm[:, None]
+    out["dG2"], out["dG2_bound"] = dZ.T @ H1, gemm_bound(R, np.abs(dZ).T @ np.abs(H1))
+    out["dG1"], out["dG1_bound"] = dP1g.T @ y, gemm_bound(R, np.abs(dP1g).T @ np.abs(y))
+    out["db1"], out["db1_bound"] = dP1g.sum(0), gemm_bound(R, np.abs(dP1g).sum(0))
+    return out
+
+
+# ---- the case table.  Ids come from the universe [0, HL_N); a case's Z rows
+# are seeded Gaussians (rows of a fresh model are nearly collapsed: the
+# cotangent, a difference of nearly equal unit vectors, is then no fair fp32
+# target).  Seeds are fixed so that every |hinge argument| >= ARG_MIN
+# (tests/test_host.py checks it).
+HAND_MULTS = (1, 1, 2, 3, 4, 5, 12, 13, 16, 17, 20, 21, 33)   # besides the query node's B + 2
+HAND_B = 75
+
+
+def hand_batch(seed=0):
+    """One batch built by hand, B = 75 (225 positions, 14 nodes).  Multiplicity
+    over all three calls, per node: 77 (node Q: every query position, the
+    positive of one triple -- q == p -- and the negative of another: all three
+    groups), then 1 (positive only), 1 (negative only), 2 and 4 (planted ties:
+    positive and negative of the same triple(s); hinge exactly 0 at margin 0),
+    3 (node X, positives only; hand_Z puts X beside Q, so its triples are all
+    inactive), 5 and 17 (negatives only), 13 and 21 (positives only), 12, 16,
+    20, 33 (both).  Returns (batch [B][3] int64, roles)."""
+    rng = np.random.default_rng(1000 + seed)
+    node = rng.choice(HL_N, 14, replace=False).astype(np.int64)
+    Q, a1, b1, y2, X, y4, n5, m12, p13, m16, n17, m20, p21, m33 = node
+    P = [a1] + [X] * 3 + [p13] * 13 + [p21] * 21 + [m12] * 4 + [m16] * 8 + [m20] * 9 + [m33] * 12
+    N = [b1] + [n5] * 5 + [n17] * 17 + [m12] * 8 + [m16] * 8 + [m20] * 11 + [m33] * 21
+    assert len(P) == len(N) == 71  # 70 pairs, the q == p triple's negative and the n == Q triple's positive
+    while True:
+        P2, N2 = list(rng.permutation(P)), list(rng.permutation(N))
+        # triple 0: q == p (its negative from the pool); triple 1: n == Q (its positive from the pool)
+        tri = [(Q, Q, N2.pop())] + [(Q, P2.pop(), Q)] + [(Q, y2, y2), (Q, y4, y4), (Q, y4, y4)]
+        tri += [(Q, p, n) for p, n in zip(P2, N2)]
+        t = np.array(tri, np.int64)
+        if (t[5:, 1] != t[5:, 2]).all() and t[1, 1] != X:  # no accidental tie; X never beside n == Q
+            break
+    assert len(t) == HAND_B
+    t = t[rng.permutation(HAND_B)]
+    return t, dict(Q=int(Q), X=int(X), ties=(int(y2), int(y4)), nodes=node)
+
+
+def pool_batch(B, S, seed, heavy=False):
+    """[B][3] ids over a pool of S nodes, every one present; heavy: Zipf-like
+    repeats (a few nodes take most positions)"""
+    rng = np.random.default_rng(2000 + seed)
+    pool = rng.choice(HL_N, S, replace=False).astype(np.int64)
+    w = 1.0 / np.arange(1, S + 1) ** (1.5 if heavy else 0.0)
+    rest = rng.choice(pool, 3 * B - S, p=w / w.sum())
+    return rng.permutation(np.concatenate([pool, rest])).reshape(B, 3)
+
+
+def case_Z(case, batch):
+    """seeded Gaussian float32 rows [R][out] by rank; the hand batch: X's row
+    beside Q's (cos(Q, X) ~ 1: X's triples, all with X as the positive, are
+    inactive)"""
+    S = np.unique(batch)
+    rng = np.random.default_rng(3000 + case["seed"])
+    Z = rng.standard_normal((len(S), case["out"])).astype(np.float32)
+    if case["kind"] == "hand":
+        _, roles = hand_batch()
+        q, xr = np.searchsorted(S, roles["Q"]), np.searchsorted(S, roles["X"])
+        Z[xr] = 2 * Z[q] + np.float32(0.05) * Z[xr]
+    return Z
+
+
+def case_batch(case):
+    if case["kind"] == "hand":
+        return hand_batch()[0]
+    return pool_batch(case["B"], case["S"], case["seed"], heavy=case["kind"] == "heavy")
+
+
+def _case(name, kind, out, B, S, seed, margin=0.3, d_in=None, mon=1, rep_sum=1):
+    return dict(name=name, kind=kind, out=out, B=B, S=S, seed=seed, margin=margin,
+                d_in=d_in or max(out, 4), mon=mon, rep_sum=rep_sum)
+
+
+# (seed: the first of 0, 1, 2, ... with every |arg| >= ARG_MIN, found on the host)
+LOSS_CASES = (
+    # every batch size (B % 4 in 0 .. 3: the monitor's last block of 1 .. 4 triples), every width
+    [_case(f"B{B}-S{S}-o{o}", "pool", o, B, S, sd) for B, S, o, sd in (
+        (2, 1, 4, 0), (3, 9, 8, 0), (4, 7, 16, 3), (5, 11, 32, 0), (7, 13, 64, 0), (8, 20, 128, 4), (9, 17, 4, 0),
+        # top sets on both sides of the head's 32-row blocks
+        (64, 31, 8, 0), (64, 32, 128, 0), (64, 33, 32, 0), (64, 64, 16, 0), (64, 65, 64, 0),
+        (129, 200, 128, 0), (129, 200, 4, 0))] +
+    # the hand-built batch: both places the repeated ranks are summed, every width
+    [_case(f"hand-o{o}-rs{rs}", "hand", o, HAND_B, 14, 0, margin=0.0, rep_sum=rs)
+     for o in (4, 8, 16, 32, 64, 128) for rs in (1, 0)] +
+    # the feature monitor's register widths and its streamed tail (d_in > 1024), B % 4 != 0
+    [_case(f"feat{d}-mon{m}", "pool", 4, 7, 13, 0, d_in=d, mon=m)
+     for d in (4, 128, 132, 256, 260, 512, 1024, 1028) for m in ((1, 0) if d in (4, 1028) else (1,))] +
+    [_case("feat132-B129", "pool", 4, 129, 200, 0, d_in=132)] +
+    # no position CSR: float atomics into G
+    [_case("atomic-16386", "heavy", 8, 5462, 50, 1)])
+
+# the head cases (top-set rows on both sides of the kernels' 32- and 16-row blocks; widths whose
+# lane mask cuts inside a wave and whose clamps min(c, o - 4) / min(row, o - 1) decide)
+HEAD_SEPARATE_WIDTHS = (4, 12, 32, 100, 124, 128)
+HEAD_SEPARATE_ROWS = (1, 31, 32, 33, 65, 200)
+HEAD128_FORMS = ("in-tile", "in-tile-off", "k192")   # (d_in, hid) = (128, 128), the same with the knob off, (128, 64)
+HEAD128_ROWS = (1, 15, 16, 17, 33)
+BACKWARD_WIDTHS = (4, 32, 128)                       # after a loss (the loss needs a width dividing 1024)
+AUTOGRAD_WIDTHS = (4, 12, 100, 128)                  # from an output gradient
+AUTOGRAD_MULTS = (1, 2, 3, 4, 5, 12, 13, 16, 17, 20, 21, 33)

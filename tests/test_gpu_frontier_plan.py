@@ -39,7 +39,7 @@ import numpy as np
 import pytest
 import torch
 
-from parity_util import POS_CSR_MAX, check_frontier_plan, frontier_plan_reference
+from parity_util import POS_CSR_MAX, check_frontier_plan, frontier_plan_reference, perm_table
 
 pytestmark = pytest.mark.gpu
 
@@ -75,17 +75,6 @@ def arith_table(n, T, ld, a, seed):
         nb[:, t] = ((i * a + offs[t]) % n).to(torch.int32)
         wb[:, t] = _hash_bits(i, t, seed)
     return nb, wb
-
-
-def perm_table(n, T, ld, seed):
-    """small universes: nb[i][t] = (p[i] + t) % n over a random permutation p
-    (every column is a permutation: a frontier over all rows is the universe)"""
-    assert T <= n
-    rng = np.random.default_rng(seed)
-    p = rng.permutation(n)
-    nb = (p[:, None] + np.arange(ld)[None, :]) % n
-    wb = rng.integers(0, 1 << 32, (n, ld), dtype=np.uint64).astype(np.uint32).view(np.int32)
-    return torch.from_numpy(nb.astype(np.int32)).to(DEVICE), torch.from_numpy(wb).to(DEVICE)
 
 
 def plant_rows(nb, members, T):

@@ -587,3 +587,260 @@ def test_bench_dump_outputs_writes_float32_within_its_budget(tmp_path):
     assert np.isin(small["param.0.weight.npy"], got["param.0.weight.npy"]).all()
     assert np.array_equal(small["param.0.bias.npy"], got["param.0.bias.npy"])
     assert sorted(small) == sorted(again) and all(np.array_equal(small[k], again[k]) for k in small)
+
+
+# ----------------------------------------------------------------------------- loss / head references
+def _loss_case_inputs(case):
+    import parity_util as pu
+    batch = pu.case_batch(case)
+    Z = pu.case_Z(case, batch)
+    S = np.unique(batch)
+    pr = np.searchsorted(S, batch.reshape(-1))
+    return pu, batch, Z, S, pr
+
+
+def _loss_case_ids():
+    import parity_util as pu
+    return [pytest.param(c, id=c["name"]) for c in pu.LOSS_CASES]
+
+
+@pytest.mark.parametrize("case", _loss_case_ids())
+def test_loss_reference_matches_autograd(case):
+    """parity_util.loss_reference against torch float64 autograd of the
+    project's max_margin_loss over rows gathered per position, the oracle's
+    put_embeddings (_put: index_put's backward) and the gather doing the sums
+    over repeated ids: loss and dZ to 1e-12 relative."""
+    import pinsage_training as pt
+    from oracle import oracle as orc
+    pu, batch, Z, S, pr = _loss_case_inputs(case)
+    B, d = case["B"], case["out"]
+    ref = pu.loss_reference(Z, pr, B, case["margin"])
+    Zt = torch.tensor(Z.astype(np.float64), requires_grad=True)
+    hs = []
+    for c in range(3):
+        idc = torch.from_numpy(np.ascontiguousarray(batch[:, c]))
+        rows = Zt[torch.from_numpy(np.ascontiguousarray(pr.reshape(B, 3)[:, c]))]
+        hs.append(orc._put(torch.zeros(pu.HL_N, d, dtype=torch.float64), idc, rows)[idc])
+    loss = pt.max_margin_loss(*hs, case["margin"])
+    loss.backward()
+    assert abs(float(loss.detach()) - ref["loss"]) <= 1e-12 * abs(ref["loss"])
+    g = Zt.grad.numpy()
+    assert np.linalg.norm(g - ref["dZ"]) <= 1e-12 * np.linalg.norm(ref["dZ"])
+    assert np.linalg.norm(ref["dZ"]) > 0 or len(S) == 1  # (all ids equal: every cotangent is zero)
+
+
+@pytest.mark.parametrize("case", _loss_case_ids())
+def test_loss_cases_reach_what_they_claim(case):
+    pu, batch, Z, S, pr = _loss_case_inputs(case)
+    B = case["B"]
+    assert batch.shape == (B, 3) and len(S) == case["S"] and Z.dtype == np.float32
+    assert (3 * B > pu.POS_CSR_MAX) == (case["kind"] == "heavy")
+    ref = pu.loss_reference(Z, pr, B, case["margin"])
+    arg32 = pu.hinge_replay32(Z, pr, B, case["margin"])
+    ties = batch[:, 1] == batch[:, 2] if case["margin"] == 0.0 else np.zeros(B, bool)
+    assert (ref["arg"][ties] == 0.0).all() and (arg32[ties] == 0.0).all()
+    assert np.abs(ref["arg"][~ties]).min() >= pu.ARG_MIN
+    assert (np.sign(arg32[~ties]) == np.sign(ref["arg"][~ties])).all()
+    if B >= 4:
+        assert ref["active"].any() and not ref["active"].all()
+    if case["kind"] != "hand":
+        return
+    _, roles = pu.hand_batch()
+    mult = np.bincount(pr)
+    assert sorted(mult) == sorted(pu.HAND_MULTS + (B + 2,)) and B == pu.HAND_B
+    assert {1, 2, 3, 4, 5, 12, 13, 16, 17, 20, 21, 33} <= set(mult.tolist())
+    assert (batch[:, 0] == roles["Q"]).all()                         # one node fills every query position
+    groups = {int(v): {c for c in range(3) if (batch[:, c] == v).any()} for v in S}
+    assert sorted({len(g) for g in groups.values()}) == [1, 2, 3]  # one, two and all three groups
+    assert int((batch[:, 0] == batch[:, 1]).sum()) == 1              # one triple with q == p
+    assert int(ties.sum()) == 3 and ref["active"][ties].all()       # p == n: hinge exactly 0, active
+    xin = (batch == roles["X"]).any(1)
+    assert int(xin.sum()) == 3 and not ref["active"][xin].any()      # a repeated node with inactive triples only
+
+
+def test_loss_case_table_covers_the_regimes():
+    import parity_util as pu
+    C = pu.LOSS_CASES
+    assert {c["out"] for c in C} == {4, 8, 16, 32, 64, 128}
+    assert {2, 3, 4, 5, 7, 8, 9, 64, 129} <= {c["B"] for c in C}
+    assert {1, 31, 32, 33, 64, 65, 200} <= {c["S"] for c in C}
+    assert {4, 128, 132, 256, 260, 512, 1024, 1028} <= {c["d_in"] for c in C}
+    assert any(c["d_in"] > 4 and c["B"] % 4 for c in C) and {0, 1} <= {c["mon"] for c in C}
+    assert [c for c in C if 3 * c["B"] == 16386 and c["out"] == 8]
+    assert len({c["name"] for c in C}) == len(C)
+    # the head: rows around its 32-row (16-row in the tile) blocks, widths off the 32-lane grid
+    assert {1, 31, 32, 33} <= set(pu.HEAD_SEPARATE_ROWS) and {15, 16, 17} <= set(pu.HEAD128_ROWS)
+    assert any(w % 32 for w in pu.HEAD_SEPARATE_WIDTHS) and all(w % 4 == 0 and w <= 128 for w in pu.HEAD_SEPARATE_WIDTHS)
+    assert all(1024 % w == 0 for w in pu.BACKWARD_WIDTHS) and any(1024 % w for w in pu.AUTOGRAD_WIDTHS)
+    assert {5, 13, 17, 21} <= set(pu.AUTOGRAD_MULTS)  # head_sum_reps: 4 + 1, 4 + 8 + 1; rep_sum: 16 + 1, 16 + 5
+
+
+def _synthetic_loss_outputs(pu, case, cap=40, all_active=False):
+    """what a correct device would leave (float32 roundings of the reference,
+    G's repeated ranks as the ordered float32 sums of the Gp rows)"""
+    _, batch, Z, S, pr = _loss_case_inputs(case)
+    B, R, d = case["B"], len(S), case["out"]
+    feats = np.random.default_rng(0).standard_normal((pu.HL_N, 8)).astype(np.float32)
+    ref = pu.loss_reference(Z, pr, B, case["margin"], feats, batch)
+    src = ref
+    if all_active:  # the defect: every triple treated as active
+        src = pu.loss_reference(Z, pr, B, 10.0)
+    Gp = src["cot"].astype(np.float32)
+    G = np.zeros((3, cap, d), np.float32)
+    for (c, r), row in pu.rep_sum32(Gp, pr, R).items():
+        G[c, r] = row
+    for r in np.flatnonzero(np.bincount(pr, minlength=R) == 1):
+        p = int(np.flatnonzero(pr == r)[0])
+        G[p % 3, r] = Gp[p]
+    Kc = np.zeros((3, cap), np.int32)
+    Kc[:, :R] = ref["K"]
+    scal = np.array([ref["loss"], ref["nfl"], ref["sumsq"], ref["var"]], np.float32)
+    return ref, pr, R, dict(hinge=ref["arg"].astype(np.float32), G=G, Kc=Kc, Gp=Gp, scal=scal)
+
+
+def test_loss_checkers_reject_single_defects():
+    import parity_util as pu
+    case = next(c for c in pu.LOSS_CASES if c["name"] == "hand-o8-rs0")
+    ref, pr, R, got = _synthetic_loss_outputs(pu, case)
+    B, cap = case["B"], got["G"].shape[1]
+
+    def dz_of(g):
+        dz, bound = pu.dz_reference(g["G"], g["Kc"], g["Gp"], pr, R, "head")
+        return dz, bound
+
+    dz, bound = dz_of(got)
+    dZ = np.zeros((cap, 8), np.float32)
+    dZ[:R] = dz
+
+    def clean():
+        pu.check_loss(got, ref, "rep_sum")
+        pu.check_loss(dict(got, G=_head_mode_G(got, ref, R)), ref, "head")
+        pu.check_rep_sum_exact(got["G"], got["Gp"], pr, R)
+        pu.check_rows("dZ", dZ, R, dz, bound)
+        # the device's own sums agree with the reference's K Gsum as well
+        assert np.abs(dz - ref["dZ"]).max() <= 1e-5 * np.abs(ref["dZ"]).max()
+
+    def _head_mode_G(g, ref, R):
+        G = g["G"].copy()
+        G[:, :R][:, ref["K"].sum(0) > 1] = 0  # the repeated ranks stay in Gp
+        return G
+
+    clean()
+    rep = int(np.flatnonzero(np.bincount(pr, minlength=R) == 13)[0])  # the 13-position rank (positives only)
+    mixed = int(np.flatnonzero(np.bincount(pr, minlength=R) == 33)[0])  # positives and negatives
+
+    # K dropped: dZ = sum_c G[c]
+    bad = np.zeros_like(dZ)
+    bad[:R] = pu.dz_reference(got["G"], np.minimum(got["Kc"], 1), got["Gp"], pr, R, "head")[0]
+    with pytest.raises(AssertionError, match=r"^dZ: .* first at row \d+, column \d+"):
+        pu.check_rows("dZ", bad, R, dz, bound)
+    # the groups p % 3 swapped (positive <-> negative)
+    sw = dict(got, G=got["G"][[0, 2, 1]].copy())
+    with pytest.raises(AssertionError, match=r"^rep_sum: call (positive|negative), rank \d+"):
+        pu.check_rep_sum_exact(sw["G"], got["Gp"], pr, R)
+    with pytest.raises(AssertionError, match=r"^G: .* first at call (positive|negative), rank \d+"):
+        pu.check_loss(sw, ref, "rep_sum")
+    bad[:R] = (got["Kc"][:, :R, None].astype(np.float64) * got["G"][[0, 2, 1]][:, :R]).sum(0)
+    with pytest.raises(AssertionError, match="^dZ: "):
+        pu.check_rows("dZ", bad, R, dz, bound)
+    # one position of a repeated rank skipped
+    skip = got["G"].copy()
+    p_skip = next(int(p) for p in np.flatnonzero(pr == rep)[4:] if ref["active"][p // 3])  # past the first four
+    assert p_skip % 3 == 1
+    skip[1, rep] = sum((got["Gp"][p] for p in np.flatnonzero(pr == rep) if p != p_skip), np.zeros(8, np.float32))
+    with pytest.raises(AssertionError, match=rf"^rep_sum: call positive, rank {rep} \(13 positions\)"):
+        pu.check_rep_sum_exact(skip, got["Gp"], pr, R)
+    with pytest.raises(AssertionError, match=rf"^G: .* first at call positive, rank {rep}"):
+        pu.check_loss(dict(got, G=skip), ref, "rep_sum")
+    bad[:R] = (got["Kc"][:, :R, None].astype(np.float64) * skip[:, :R]).sum(0)
+    with pytest.raises(AssertionError, match=rf"^dZ: .* first at row {rep}, column"):
+        pu.check_rows("dZ", bad, R, dz, bound)
+    # an inactive triple counted as active
+    _, _, _, wrong = _synthetic_loss_outputs(pu, case, all_active=True)
+    with pytest.raises(AssertionError, match=r"^(G|Gp): "):
+        pu.check_loss(dict(got, G=wrong["G"], Gp=wrong["Gp"]), ref, "rep_sum")
+    with pytest.raises(AssertionError, match=r"^Gp: .* first at position \d+ \(triple \d+, call \w+, rank \d+\)"):
+        pu.check_loss(dict(got, G=_head_mode_G(got, ref, R), Gp=wrong["Gp"]), ref, "head")
+    # an inactive triple's Gp rows left as they were (garbage), a tie's hinge not exactly zero, Kc off by one
+    garbage = got["Gp"].copy()
+    garbage[np.flatnonzero((pr == mixed) & ~np.repeat(ref["active"], 3))[0]] = np.nan
+    with pytest.raises(AssertionError, match="^Gp: "):
+        pu.check_loss(dict(got, Gp=garbage), ref, "rep_sum")
+    h = got["hinge"].copy()
+    h[np.flatnonzero(ref["arg"] == 0.0)[0]] = 1e-9
+    with pytest.raises(AssertionError, match="^hinge of the planted ties"):
+        pu.check_loss(dict(got, hinge=h), ref, "rep_sum")
+    h = got["hinge"].copy()
+    h[np.flatnonzero(ref["arg"] == 0.0)[0]] = -1e-9
+    with pytest.raises(AssertionError, match="^hinge of the planted ties"):
+        pu.check_loss(dict(got, hinge=h), ref, "rep_sum")
+    k = got["Kc"].copy()
+    k[2, R] = 1
+    with pytest.raises(AssertionError, match=rf"^Kc: .* first at call negative, rank {R}"):
+        pu.check_loss(dict(got, Kc=k), ref, "rep_sum")
+    clean()
+    # the variance divided by B (a batch whose query rows differ: the hand batch's variance is 0)
+    case9 = next(c for c in pu.LOSS_CASES if c["name"] == "B9-S17-o4")
+    ref9, _, _, got9 = _synthetic_loss_outputs(pu, case9)
+    pu.check_loss(got9, ref9, "rep_sum")
+    s = got9["scal"].copy()
+    s[3] *= 8 / 9
+    with pytest.raises(AssertionError, match=r"^scalar 3 \(variance\)"):
+        pu.check_loss(dict(got9, scal=s), ref9, "rep_sum")
+
+
+def test_head_checkers_reject_single_defects():
+    import parity_util as pu
+    rng = np.random.default_rng(5)
+    R, cap, o = 33, 40, 12
+    y = rng.standard_normal((R, o)).astype(np.float32)
+    y /= np.linalg.norm(y, axis=1, keepdims=True)
+    G1w, G2w = (rng.standard_normal((o, o)).astype(np.float32) / np.sqrt(o) for _ in range(2))
+    G1b = (rng.standard_normal(o) / np.sqrt(o)).astype(np.float32)
+    sent = np.uint32(0x7FC12345)
+
+    def full(rows):
+        a = np.full((cap, o), sent, np.uint32).view(np.float32)
+        a[:R] = rows
+        return a
+
+    H1 = full(pu.head_reference_fwd(y, G1w, G1b, G2w, np.zeros((R, o)))["H1"].astype(np.float32))
+    ref = pu.head_reference_fwd(y, G1w, G1b, G2w, H1[:R])
+    Z = full(ref["Z"].astype(np.float32))
+    assert pu.check_rows("H1", H1, R, ref["H1"], ref["H1_bound"], sent) <= 1.0
+    assert pu.check_rows("Z", Z, R, ref["Z"], ref["Z_bound"], sent) <= 1.0
+    # one row past a 32-row block left unwritten
+    bad = H1.copy()
+    bad[32] = np.full(o, sent, np.uint32).view(np.float32)
+    with pytest.raises(AssertionError, match="^H1: 12 of 396 entries outside their bound, first at row 32, column 0"):
+        pu.check_rows("H1", bad, R, ref["H1"], ref["H1_bound"], sent)
+    # one column past o written: the last live row's lands past the live rows, another row's in the next row
+    bad = Z.copy()
+    bad.reshape(-1)[(R - 1) * o + o] = 0.0
+    with pytest.raises(AssertionError, match=rf"^Z past its {R} live rows: 1 of .* first at row {R}, column 0"):
+        pu.check_rows("Z", bad, R, ref["Z"], ref["Z_bound"], sent)
+    bad = Z.copy()
+    bad.reshape(-1)[7 * o + o] = 0.0
+    with pytest.raises(AssertionError, match="^Z: 1 of 396 entries outside their bound, first at row 8, column 0"):
+        pu.check_rows("Z", bad, R, ref["Z"], ref["Z_bound"], sent)
+    # an error of a few units in the last place of the terms is a failure: the bound is not slack
+    bad = Z.copy()
+    bad[5, 3] += np.float32(4 * (o + 4) * pu.U24 * (np.abs(H1[5].astype(np.float64)) @ np.abs(G2w[3].astype(np.float64))))
+    with pytest.raises(AssertionError, match="^Z: 1 of 396 entries outside their bound, first at row 5, column 3"):
+        pu.check_rows("Z", bad, R, ref["Z"], ref["Z_bound"], sent)
+    # the backward's reference is consistent with autograd (float64) through the same chain
+    dZ = rng.standard_normal((R, o)).astype(np.float32)
+    nrm = (rng.random(R) + 0.5).astype(np.float32)
+    pre = torch.tensor(rng.standard_normal((R, o)), requires_grad=True)
+    u = torch.nn.functional.leaky_relu(pre, 0.01)
+    yt = u / u.norm(dim=1, keepdim=True)
+    G1t, b1t, G2t = (torch.tensor(a.astype(np.float64), requires_grad=True) for a in (G1w, G1b, G2w))
+    H1t = torch.nn.functional.leaky_relu(yt @ G1t.t() + b1t, 0.01)
+    (H1t @ G2t.t() * torch.tensor(dZ.astype(np.float64))).sum().backward()
+    d64 = pu.head_reference_bwd(dZ, H1t.detach().numpy(), yt.detach().numpy(), u.norm(dim=1).detach().numpy(),
+                                G1w, G2w, np.zeros((R, o)))
+    dP1 = d64["dP1"]
+    d64 = pu.head_reference_bwd(dZ, H1t.detach().numpy(), yt.detach().numpy(), u.norm(dim=1).detach().numpy(),
+                                G1w, G2w, dP1)
+    for got, want in ((d64["dp"], pre.grad), (d64["dG2"], G2t.grad), (d64["dG1"], G1t.grad), (d64["db1"], b1t.grad)):
+        assert np.abs(got - want.numpy()).max() <= 1e-12 * np.abs(want.numpy()).max()
