@@ -54,8 +54,34 @@ class EngineHeadOffsets(ctypes.Structure):
                 ("Gp", i64), ("cap", i64)]
 
 
+class GemmParams(ctypes.Structure):
+    """pinsage_gemm_params_t: every field of one GEMM launch (test entry)."""
+    _fields_ = [("size", i64), ("M", i64), ("N", i64), ("K", i64), ("M_dev", vp), ("K_dev", vp),
+                ("M_max", i64), ("K_max", i64), ("a_kmajor", i64), ("b_kmajor", i64), ("a", vp), ("lda", i64),
+                ("a_idx", vp), ("K1", i64), ("a2", vp), ("lda2", i64), ("a2_idx", vp), ("b", vp), ("ldb", i64),
+                ("b_idx", vp), ("N1", i64), ("b2", vp), ("ldb2", i64), ("b2_idx", vp), ("c", vp), ("ldc", i64),
+                ("c_idx", vp), ("c2", vp), ("ldc2", i64), ("bias_part", vp), ("epi", i64), ("bias", vp),
+                ("act", i64), ("mask", vp), ("ldm", i64), ("norms", vp), ("splits", i64), ("M_hint", i64),
+                ("cfg", i64), ("sk_slab", vp), ("sk_cnt", vp), ("sk_cnt_len", i64), ("stream_k", i64),
+                ("sk_min_units", i64), ("prec", i64), ("b_split", vp), ("ldb_split", i64), ("a_ilv", vp),
+                ("b_ilv", vp), ("lda_ilv", i64), ("ldb_ilv", i64)]
+
+    def __init__(self, **kw):
+        super().__init__(size=ctypes.sizeof(GemmParams), a_kmajor=1, b_kmajor=1, K1=-1, N1=-1, splits=1, cfg=-1,
+                         stream_k=-1, sk_min_units=4, prec=-1)
+        for k, v in kw.items():
+            setattr(self, k, v)
+
+
 # name -> (restype, argtypes)
 _SIGS = {
+    "pinsage_gemm_sk_slab_floats": (i64, []),
+    "pinsage_gemm_params": (ctypes.c_int, [ctypes.POINTER(GemmParams), ctypes.POINTER(ctypes.c_int), vp]),
+    "pinsage_reduce_slabs": (ctypes.c_int, [vp, i64, i64, i64, i64, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp,
+                                            ctypes.c_double, ctypes.c_double, ctypes.c_float, vp]),
+    "pinsage_adam": (ctypes.c_int, [vp, vp, vp, vp, i64, vp, ctypes.c_double, ctypes.c_double, ctypes.c_float,
+                                    vp]),
+    "pinsage_norm_lrelu_backward_ex": (ctypes.c_int, [vp, vp, vp, vp, i64, i64, vp, vp, i64, vp, vp, i64, vp]),
     "pinsage_version": (ctypes.c_int, []),
     "pinsage_last_error": (ctypes.c_char_p, []),
     "pinsage_device_count": (ctypes.c_int, []),

@@ -57,6 +57,9 @@ int launch_set_rank_table(const int64_t*, int64_t, const int32_t*, int64_t, int,
                           const uint32_t*, int32_t*, hipStream_t);
 int launch_norm_lrelu_bwd(const float*, const float*, const float*, int, const int*, int64_t, float*, float*,
                           int, const int*, int*, int64_t, hipStream_t);
+int launch_adam(float*, const float*, float*, float*, int64_t, const float*, double, double, float, hipStream_t);
+int launch_reduce_slabs_2d(const float*, int, int64_t, int, int, float*, int64_t, const float*, float*,
+                           const AdamSlice*, hipStream_t);
 int csr_prepare();
 int launch_csr_build(const int32_t*, const float*, const int*, int64_t, int, const int*, int64_t, int*, int*,
                      int*, int*, int*, int2*, int2*, int*, int2*, int*, float*, int, hipStream_t, int2*);
@@ -997,6 +1000,121 @@ int pinsage_norm_lrelu_backward(const float* y, const float* norms, const float*
   }
   if (n == 0) return kOk;
   return launch_norm_lrelu_bwd(y, norms, dy, (int)out, nullptr, n, dp, nullptr, 0, nullptr, nullptr, 0,
+                               (hipStream_t)stream);
+}
+
+// ------------------------------------------------------------------ test entries
+int64_t pinsage_gemm_sk_slab_floats(void) { return gemm_sk_slab_floats(); }
+
+int pinsage_gemm_params(const pinsage_gemm_params_t* q, int* ran_stream_k, void* stream) {
+  if (ran_stream_k) *ran_stream_k = 0;
+  PS_REQUIRE(q && q->size == (int64_t)sizeof(pinsage_gemm_params_t), kErrArg,
+             "gemm_params: null or a struct of another size");
+  auto fits = [](int64_t v) { return v >= -1 && v <= INT32_MAX; };
+  PS_REQUIRE(fits(q->M) && fits(q->N) && fits(q->K) && fits(q->M_max) && fits(q->K_max) && fits(q->K1) &&
+                 fits(q->N1) && fits(q->splits) && fits(q->M_hint) && fits(q->sk_min_units) && q->M >= 0 &&
+                 q->K >= 0 && q->M_max >= 0 && q->K_max >= 0 && q->splits >= 1 && q->M_hint >= 0,
+             kErrArg, "gemm_params: a size out of range");
+  PS_REQUIRE(q->epi >= kEpiStore && q->epi <= kEpiPartial && q->cfg >= -1 && q->cfg <= 5 && q->stream_k >= -1 &&
+                 q->stream_k <= 1 && q->prec >= -1 && q->prec <= 1,
+             kErrArg, "gemm_params: epi 0..3, cfg -1..5, stream_k -1..1, prec -1..1");
+  PS_REQUIRE((q->a || q->a_ilv) && (q->b || q->b_ilv) && q->c, kErrArg, "gemm_params: a, b and c must be set");
+  PS_REQUIRE((q->sk_slab != nullptr) == (q->sk_cnt != nullptr) && (!q->sk_cnt || q->sk_cnt_len > 0), kErrArg,
+             "gemm_params: stream-K scratch needs the slab, the tickets and their count");
+  GemmParams p;
+  p.M = (int)q->M;
+  p.N = (int)q->N;
+  p.K = (int)q->K;
+  p.M_dev = q->M_dev;
+  p.K_dev = q->K_dev;
+  p.M_max = (int)q->M_max;
+  p.K_max = (int)q->K_max;
+  p.a_kmajor = q->a_kmajor != 0;
+  p.b_kmajor = q->b_kmajor != 0;
+  p.a = q->a;
+  p.lda = q->lda;
+  p.a_idx = q->a_idx;
+  p.K1 = (int)q->K1;
+  p.a2 = q->a2;
+  p.lda2 = q->lda2;
+  p.a2_idx = q->a2_idx;
+  p.b = q->b;
+  p.ldb = q->ldb;
+  p.b_idx = q->b_idx;
+  p.N1 = (int)q->N1;
+  p.b2 = q->b2;
+  p.ldb2 = q->ldb2;
+  p.b2_idx = q->b2_idx;
+  p.c = q->c;
+  p.ldc = q->ldc;
+  p.c_idx = q->c_idx;
+  p.c2 = q->c2;
+  p.ldc2 = q->ldc2;
+  p.bias_part = q->bias_part;
+  p.epi = (int)q->epi;
+  p.bias = q->bias;
+  p.act = q->act != 0;
+  p.mask = q->mask;
+  p.ldm = q->ldm;
+  p.norms = q->norms;
+  p.splits = (int)q->splits;
+  p.M_hint = (int)q->M_hint;
+  p.cfg = (int)q->cfg;
+  p.sk_slab = q->sk_slab;
+  p.sk_cnt = q->sk_cnt;
+  p.sk_cnt_len = q->sk_cnt_len;
+  p.stream_k = (int)q->stream_k;
+  p.sk_min_units = (int)q->sk_min_units;
+  p.prec = (int)q->prec;
+  p.b_split = q->b_split;
+  p.ldb_split = q->ldb_split;
+  p.a_ilv = q->a_ilv;
+  p.b_ilv = q->b_ilv;
+  p.lda_ilv = q->lda_ilv;
+  p.ldb_ilv = q->ldb_ilv;
+  const int rc = launch_gemm(p, (hipStream_t)stream);
+  if (ran_stream_k) *ran_stream_k = gemm_last_stream_k();
+  return rc;
+}
+
+int pinsage_reduce_slabs(const float* part, int64_t S, int64_t stride, int64_t M, int64_t N, float* out,
+                         int64_t ld, const float* bpart, float* bias_out, float* adam_p, float* adam_m,
+                         float* adam_v, float* adam_pb, float* adam_mb, float* adam_vb, const float* coef,
+                         double beta1, double beta2, float eps, void* stream) {
+  PS_REQUIRE(part && out && S >= 1 && S <= INT32_MAX && M > 0 && N > 0 && M <= INT32_MAX && N <= INT32_MAX &&
+                 ld >= N && stride >= M * N && (!bias_out || bpart),
+             kErrArg, "reduce_slabs: bad argument");
+  AdamSlice ad;
+  if (adam_p) {
+    ad.p = adam_p;
+    ad.m = adam_m;
+    ad.v = adam_v;
+    ad.pb = adam_pb;
+    ad.mb = adam_mb;
+    ad.vb = adam_vb;
+    ad.coef = coef;
+    ad.beta1 = beta1;
+    ad.beta2 = beta2;
+    ad.eps = eps;
+  }
+  return launch_reduce_slabs_2d(part, (int)S, stride, (int)M, (int)N, out, ld, bpart, bias_out,
+                                adam_p ? &ad : nullptr, (hipStream_t)stream);
+}
+
+int pinsage_adam(float* p, const float* g, float* m, float* v, int64_t n, const float* coef, double beta1,
+                 double beta2, float eps, void* stream) {
+  PS_REQUIRE(p && g && m && v && coef && n >= 0, kErrArg, "adam: bad argument");
+  if (n == 0) return kOk;
+  return launch_adam(p, g, m, v, n, coef, beta1, beta2, eps, (hipStream_t)stream);
+}
+
+int pinsage_norm_lrelu_backward_ex(const float* y, const float* norms, const float* dy, const int* nrows,
+                                   int64_t n_max, int64_t out, float* dp, float* z, int64_t z_n,
+                                   const int* z_rows, int* zi, int64_t zi_n, void* stream) {
+  PS_REQUIRE(n_max >= 0 && out > 0 && out <= INT32_MAX && z_n >= 0 && z_n <= INT32_MAX && zi_n >= 0 &&
+                 (!z || z_rows),
+             kErrArg, "norm_lrelu_backward_ex: bad sizes");
+  return launch_norm_lrelu_bwd(y, norms, dy, (int)out, nrows, n_max, dp, z, (int)z_n, z_rows, zi, zi_n,
                                (hipStream_t)stream);
 }
 

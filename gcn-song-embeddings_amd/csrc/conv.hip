@@ -1808,7 +1808,10 @@ __global__ __launch_bounds__(256) void reduce_slabs_2d_kernel(const float* __res
                                    (a.z + b.z) + (c.z + d.z), (a.w + b.w) + (c.w + d.w));
       const int64_t e = e4 * 4, m = e / N, n = e - m * N, o = m * ld + n;
       *reinterpret_cast<float4*>(out + o) = r;
-      if (ad.p && bc2 > 0.f) {  // the slice's Adam step, as adam_kernel would apply it (bc2 0: refused)
+      // the slice's Adam step, as adam_kernel would apply it (bc2 0: refused) -- to the last
+      // bits, not bit for bit: the compiler contracts adam1's v update differently here, in
+      // adam_kernel's float4 body and in its scalar tail
+      if (ad.p && bc2 > 0.f) {
         float4 pp = *reinterpret_cast<const float4*>(ad.p + o);
         float4 mm = *reinterpret_cast<const float4*>(ad.m + o);
         float4 vv = *reinterpret_cast<const float4*>(ad.v + o);

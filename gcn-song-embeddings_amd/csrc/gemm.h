@@ -44,7 +44,11 @@ struct GemmParams {
   const int32_t* b2_idx = nullptr;
   float* c = nullptr;
   int64_t ldc = 0;
-  const int32_t* c_idx = nullptr;  // output row scatter
+  // output row scatter: row m goes to C row c_idx[m].  PRECONDITION (not
+  // checked): the rows are DISTINCT -- the epilogue loads what it accumulates
+  // onto and stores without atomics, and tiles run concurrently, so a repeated
+  // row loses updates.  The engine's self_src / q_src index the members of a set.
+  const int32_t* c_idx = nullptr;
   // split output (kEpiStore/kEpiAccum): columns n >= N1 are stored plainly to
   // c2[m][n - N1] instead of C (so one launch can scatter-add one block of
   // columns and write the rest)

@@ -441,6 +441,122 @@ int pinsage_concat_linear_l2norm(const float* h, int64_t ldh, const int32_t* sel
 int pinsage_norm_lrelu_backward(const float* y, const float* norms, const float* dy, int64_t n, int64_t out,
                                 float* dp, void* stream);
 
+/* ------------------------------------------------------------------ test entries
+ * Nothing in the engine or the Python package's product path calls these: they
+ * expose the engine's own launches, one at a time, to the tests
+ * (tests/test_gpu_gemm_forms.py, tests/test_gpu_optimizer.py).
+ *
+ * pinsage_gemm_params: one GEMM launch with every field of the library's
+ * launch parameters (csrc/gemm.h GemmParams, which documents them) given by
+ * the caller.  size = sizeof(pinsage_gemm_params_t) comes first (a mismatch is
+ * refused); every other member is an int64_t or a pointer, flags are 0 / 1,
+ * "unset" is -1 for K1, N1, cfg, stream_k and prec and 0 / NULL elsewhere
+ * (splits and sk_min_units: at least 1).  In short, C = op(A) op(B):
+ *   a_kmajor 1: A(m,k) = a[row(m) lda + k], row(m) = a_idx ? a_idx[m] : m; for
+ *               k >= K1 >= 0 from a2 / lda2 / a2_idx at column k - K1
+ *            0: A(m,k) = a[row(k) lda + m], row(k) = a_idx ? a_idx[k] : k
+ *   b_kmajor 1: B(k,n) = b[n ldb + k]
+ *            0: B(k,n) = b[row(k) ldb + n], row(k) = b_idx ? b_idx[k] : k; for
+ *               n >= N1 >= 0 from b2 / ldb2 / b2_idx at column n - N1
+ *   M = *M_dev <= M_max and K = *K_dev <= K_max when set (device-side counts;
+ *   M_hint only picks the tile); rows >= M are not written.
+ *   epi 0: c[dst(m) ldc + n] = f(acc + bias[n]), f = LeakyReLU when act, times
+ *          lrelu'(mask[m ldm + n]) when mask (x > 0 ? 1 : 0.01); dst(m) =
+ *          c_idx ? c_idx[m] : m.  With c2: columns n >= N1 go to
+ *          c2[m ldc2 + n - N1] instead, by row m, stored plainly.
+ *       1: the same added to c's previous value (c2's columns are still plain
+ *          stores).  A mask with epi 1 is refused.
+ *       2: v = lrelu(acc + bias), norms[m] = ||v||, c[dst(m) ldc + n] = v / ||v||
+ *          (N <= 128).
+ *       3: split-K slabs c[s][M][ldc] of the `splits` k ranges (K cut into runs
+ *          of ceil(K / splits) rounded up to 32; an empty run's slab is zero),
+ *          bias_part[s][M] = sums over the run's k of A(m,k) (M-major A).
+ *   PRECONDITION the kernels do not check: c_idx names DISTINCT rows.  A tile's
+ *   epilogue loads what it accumulates onto and stores without atomics, and
+ *   tiles of different workgroups run concurrently: a repeated row loses
+ *   updates.  The engine's self_src and q_src index the members of a set.
+ *   sk_slab / sk_cnt / sk_cnt_len: stream-K scratch of the caller's,
+ *   pinsage_gemm_sk_slab_floats() floats and sk_cnt_len ints, zeroed once (the
+ *   tickets reset themselves); stream_k 1 forces the schedule where the launch
+ *   allows it (cfg 1 or 2), 0 forbids it.  prec 0: fp32 MFMA, 1: split bf16,
+ *   -1: the process default.  *ran_stream_k (nullable) = 1 if the launch ran
+ *   the stream-K schedule, else 0. */
+typedef struct {
+  int64_t size;
+  int64_t M, N, K;
+  const int* M_dev;
+  const int* K_dev;
+  int64_t M_max, K_max;
+  int64_t a_kmajor, b_kmajor;
+  const float* a;
+  int64_t lda;
+  const int32_t* a_idx;
+  int64_t K1;
+  const float* a2;
+  int64_t lda2;
+  const int32_t* a2_idx;
+  const float* b;
+  int64_t ldb;
+  const int32_t* b_idx;
+  int64_t N1;
+  const float* b2;
+  int64_t ldb2;
+  const int32_t* b2_idx;
+  float* c;
+  int64_t ldc;
+  const int32_t* c_idx;
+  float* c2;
+  int64_t ldc2;
+  float* bias_part;
+  int64_t epi;
+  const float* bias;
+  int64_t act;
+  const float* mask;
+  int64_t ldm;
+  float* norms;
+  int64_t splits;
+  int64_t M_hint;
+  int64_t cfg;
+  float* sk_slab;
+  int* sk_cnt;
+  int64_t sk_cnt_len;
+  int64_t stream_k;
+  int64_t sk_min_units;
+  int64_t prec;
+  const uint16_t* b_split;
+  int64_t ldb_split;
+  const uint16_t* a_ilv;
+  const uint16_t* b_ilv;
+  int64_t lda_ilv, ldb_ilv;
+} pinsage_gemm_params_t;
+int64_t pinsage_gemm_sk_slab_floats(void);
+int pinsage_gemm_params(const pinsage_gemm_params_t* params, int* ran_stream_k, void* stream);
+/* The split-K reduction of the weight gradients' fallback path:
+ *   out[m ld + n] = sum over s < S of part[s stride + m N + n],
+ *   bias_out[m]   = sum over s of bpart[s M + m]     (bpart / bias_out nullable)
+ * in a fixed order: group g = 0..3 sums slabs g, g + 4, ... -- sixteen slabs
+ * at a time as acc += (x0 + x1) + (x2 + x3), the rest one by one -- and the
+ * groups combine as (g0 + g1) + (g2 + g3).  N, ld, stride multiples of 4,
+ * 16-B aligned buffers.  With adam_p set, torch.optim.Adam's step is applied
+ * to the slice from the reduced gradient (adam_p / adam_m / adam_v in out's
+ * layout, adam_pb / adam_mb / adam_vb [M] with bias_out; coef as pinsage_adam). */
+int pinsage_reduce_slabs(const float* part, int64_t S, int64_t stride, int64_t M, int64_t N, float* out,
+                         int64_t ld, const float* bpart, float* bias_out, float* adam_p, float* adam_m,
+                         float* adam_v, float* adam_pb, float* adam_mb, float* adam_vb, const float* coef,
+                         double beta1, double beta2, float eps, void* stream);
+/* One torch.optim.Adam step (_single_tensor_adam) on caller buffers p, g, m, v
+ * f32 [n], 16-B aligned: coef (device) = {lr / (1 - beta1^t), sqrt(1 - beta2^t)};
+ * coef[1] == 0 leaves p, m and v untouched. */
+int pinsage_adam(float* p, const float* g, float* m, float* v, int64_t n, const float* coef, double beta1,
+                 double beta2, float eps, void* stream);
+/* pinsage_norm_lrelu_backward in the engine's form: the row count from *nrows
+ * (device; <= n_max, which sizes the grid; null: n_max rows), and the zeroing
+ * the engine folds into the launch: z[0, *z_rows * z_n) = 0 (z nullable) and
+ * zi[0, zi_n) = 0 (zi nullable). */
+int pinsage_norm_lrelu_backward_ex(const float* y, const float* norms, const float* dy, const int* nrows,
+                                   int64_t n_max, int64_t out, float* dp, float* z, int64_t z_n,
+                                   const int* z_rows, int* zi, int64_t zi_n, void* stream);
+
 /* ------------------------------------------------------------------ step hand-off
  * (PinSage.train_batch, pinsage_training.py:181-214, as ONE graph launch per step)
  * pinsage_step_stage: copy nbytes at src_off of slot (*ctr % R) of a pinned host

@@ -1051,3 +1051,406 @@ HEAD128_ROWS = (1, 15, 16, 17, 33)
 BACKWARD_WIDTHS = (4, 32, 128)                       # after a loss (the loss needs a width dividing 1024)
 AUTOGRAD_WIDTHS = (4, 12, 100, 128)                  # from an output gradient
 AUTOGRAD_MULTS = (1, 2, 3, 4, 5, 12, 13, 16, 17, 20, 21, 33)
+
+
+# ----------------------------------------------------------------------------- GEMM forms, slab reduction, Adam
+# The dense part of the layers' backward and the optimizer pass
+# (tests/test_gpu_gemm_forms.py, tests/test_gpu_optimizer.py): one GemmParams
+# launch (csrc/gemm.h) restated in float64 from the comments of that header,
+# reduce_slabs_2d_kernel's documented order in float32, torch's
+# _single_tensor_adam in float64 and norm_lrelu_bwd in float64, each with the
+# elements of every output buffer the launch may write.  tests/test_host.py
+# plants one defect at a time into a correct result and checks that each
+# checker names the buffer, row and column.
+SLOPE32 = float(np.float32(0.01))     # kSlope as the kernels hold it (0.01f)
+EPI_STORE, EPI_ACCUM, EPI_L2NORM, EPI_PARTIAL = 0, 1, 2, 3
+GEMM_TILES = {0: (128, 16), 1: (64, 32), 2: (32, 32), 3: (64, 16)}   # cfg: (block rows BM, k-depth BK)
+NAN_BITS = 0x7FC12345                 # the pre-fill of plainly stored outputs: a quiet NaN with a payload
+TINY32 = 2.0 ** -149                  # the smallest float32 step (results that underflow)
+
+
+def _rows(idx, n):
+    return np.arange(n) if idx is None else np.asarray(idx, np.int64)[:n]
+
+
+def gemm_operands(s):
+    """op(A) [M][K] and op(B) [K][N] of a launch spec, in float64, as gemm.h
+    states the layouts: K-major A rows gathered by a_idx, columns k >= K1 from
+    a2 (rows by a2_idx) at column k - K1; M-major A k-rows gathered by a_idx;
+    K-major B [N][K]; N-major B k-rows gathered by b_idx, columns n >= N1 from
+    b2 (k-rows by b2_idx) at column n - N1.  The spec holds every matrix as a
+    2-D array whose second extent is its leading dimension."""
+    M, N, K = s["M"], s["N"], s["K"]
+    a, b = np.asarray(s["a"], np.float64), np.asarray(s["b"], np.float64)
+    K1, N1 = s.get("K1", -1), s.get("N1", -1)
+    if s.get("a_kmajor", True):
+        r = _rows(s.get("a_idx"), M)
+        if K1 >= 0 and s.get("a2") is not None:
+            r2 = _rows(s.get("a2_idx"), M)
+            A = np.concatenate([a[r, :K1], np.asarray(s["a2"], np.float64)[r2, :K - K1]], 1)
+        else:
+            A = a[r, :K]
+    else:
+        A = a[_rows(s.get("a_idx"), K), :M].T
+    if s.get("b_kmajor", True):
+        B = b[:N, :K].T
+    else:
+        rk = _rows(s.get("b_idx"), K)
+        if s.get("b2") is not None:
+            rk2 = _rows(s.get("b2_idx"), K)
+            B = np.concatenate([b[rk, :N1], np.asarray(s["b2"], np.float64)[rk2, :N - N1]], 1)
+        else:
+            B = b[rk, :N]
+    assert A.shape == (M, K) and B.shape == (K, N), (A.shape, B.shape)
+    return A, B
+
+
+def gemm_terms(n, K, prec):
+    """the n of gemm_bound for a sum of n terms of which K are products, under
+    the product arithmetic prec.  0 (fp32 MFMA): n.  1 (split bf16): every
+    product is six bf16 products, each exact in float32, summed sixteen k at a
+    time inside one MFMA and added to the accumulator, so a term passes through
+    at most 16 additions inside its MFMA and the 6 ceil(K / 16) accumulator
+    updates -- more than n for short K."""
+    return n if prec == 0 else max(n, n - K + 6 * -(-K // 16) + 16)
+
+
+def _prod_bound(n, K, absprod, absall, prec, exact):
+    """gemm_bound of a sum whose products' absolute values sum to absprod (all
+    terms: absall).  Split bf16 drops mid lo, lo mid and lo lo of
+    (hi + mid + lo)(hi' + mid' + lo'), each below 2^-24 |a b|, and represents an
+    operand to 2^-26 relative: 3 2^-24 |a b| per product covers both.  exact:
+    the caller states that every operand is a small integer (exact in the hi
+    plane) and every partial sum below 2^24 -- no rounding at all."""
+    if exact:
+        return np.zeros_like(absall)
+    return gemm_bound(gemm_terms(n, K, prec), absall) + (3 * U24 * absprod if prec == 1 else 0.0)
+
+
+def gemm_form_reference(s, prec=0, exact=False):
+    """One GemmParams launch in float64.  s: M, N, K (the live sizes, device
+    side or not), a_kmajor, b_kmajor, a, a_idx, K1, a2, a2_idx, b, b_idx, N1,
+    b2, b2_idx, bias, act, mask, epi, splits, c_idx, and the PRE-FILLED output
+    buffers c, c2, norms [rows], bias_part [splits][M] (2-D arrays with the
+    leading dimension as second extent; c of a partial launch is
+    [splits * M][ldc]).  Returns {buffer: dict(want, bound, written)}: `want`
+    float64 where `written`, and where not written the launch must leave the
+    pre-fill bit for bit.
+
+    Epilogues (gemm.h): x = acc + bias[n]; LeakyReLU when act; times
+    lrelu'(mask[m][n]) = (mask > 0 ? 1 : 0.01f) when mask -- 0.0, -0.0 and
+    negative denormals take the slope; EPI_ACCUM adds c's pre-fill.  Row m goes
+    to c row c_idx[m]; with c2, columns >= N1 go to c2[m][n - N1] by row m,
+    never accumulated.  EPI_L2NORM: v = lrelu(x), norms[m] = |v|, c = v / |v|.
+    EPI_PARTIAL: slab s = the sum over k in [s kc, min(K, (s + 1) kc)), kc =
+    ceil(K / splits) rounded up to 32; bias_part[s][m] = that range's sum of
+    A(m, k); an empty range gives zeros.
+
+    Bounds.  Store / accumulate / partial: gemm_bound over the K products, the
+    bias and the accumulated pre-value, n by gemm_terms, plus _prod_bound's
+    split-bf16 term.  Stream-K needs no term of its own: its pieces start from
+    a zero accumulator (exact) and their combination is one more summation
+    order of the same K terms, which gemm_bound allows.  LeakyReLU and the
+    mask are products with 1 or 0.01f: the error scales with them and each
+    rounds once (2^-24 |result|).  L2 norm, with E the bound of v: the sum of
+    squares s2 = sum v^2 is off by sum 2 |v| E + (N + 4) u s2 (N products and
+    additions), r = sqrt(s2) by half of that over r plus u r for the root,
+    E_r = sum |v| E / r + ((N + 4) / 2 + 1) u r, and y = v / r by
+    E / r + |v| E_r / r^2 + u |y| (first order; the + 4 carries the second)."""
+    M, N, K = s["M"], s["N"], s["K"]
+    epi = s.get("epi", EPI_STORE)
+    A, B = gemm_operands(s)
+    out = {}
+
+    def blank(name):
+        pre = np.asarray(s[name])
+        return dict(want=np.full(pre.shape, np.nan), bound=np.zeros(pre.shape), written=np.zeros(pre.shape, bool))
+
+    if epi == EPI_PARTIAL:
+        S = s.get("splits", 1)
+        kc = (-(-K // S) + 31) // 32 * 32
+        c = blank("c")
+        bp = blank("bias_part") if s.get("bias_part") is not None else None
+        for sp in range(S):
+            k0, k1 = min(K, sp * kc), min(K, (sp + 1) * kc)
+            Ak, Bk = A[:, k0:k1], B[k0:k1]
+            absacc = np.abs(Ak) @ np.abs(Bk)
+            rows = slice(sp * M, (sp + 1) * M)
+            c["want"][rows, :N] = Ak @ Bk
+            c["bound"][rows, :N] = _prod_bound(k1 - k0, k1 - k0, absacc, absacc, prec, exact)
+            c["written"][rows, :N] = True
+            if bp is not None:
+                bp["want"][sp, :M] = Ak.sum(1)
+                bp["bound"][sp, :M] = 0.0 if exact else gemm_bound(k1 - k0, np.abs(Ak).sum(1))
+                bp["written"][sp, :M] = True
+        out["c"] = c
+        if bp is not None:
+            out["bias_part"] = bp
+        return out
+
+    bias = np.zeros(N) if s.get("bias") is None else np.asarray(s["bias"], np.float64)[:N]
+    x = A @ B + bias
+    absprod = np.abs(A) @ np.abs(B)
+    n = K + (s.get("bias") is not None)
+    dst = _rows(s.get("c_idx"), M)
+    c = blank("c")
+    if epi == EPI_L2NORM:
+        E = _prod_bound(n, K, absprod, absprod + np.abs(bias), prec, exact)
+        v = np.where(x > 0, x, SLOPE32 * x)
+        E = np.where(x > 0, E, SLOPE32 * E + U24 * np.abs(v))
+        r = np.sqrt((v * v).sum(1, keepdims=True))
+        E_r = (np.abs(v) * E).sum(1, keepdims=True) / r + ((N + 4) / 2 + 1) * U24 * r
+        y = v / r
+        c["want"][dst, :N] = y
+        c["bound"][dst, :N] = E / r + np.abs(v) * E_r / r ** 2 + U24 * np.abs(y)
+        c["written"][dst, :N] = True
+        out["c"] = c
+        if s.get("norms") is not None:
+            nr = blank("norms")
+            nr["want"][:M], nr["bound"][:M], nr["written"][:M] = r[:, 0], E_r[:, 0], True
+            out["norms"] = nr
+        return out
+
+    absall = absprod + np.abs(bias)
+    scale = np.ones((M, N))
+    rounds = np.zeros((M, N))
+    if s.get("act"):
+        neg = ~(x > 0)
+        x = np.where(neg, SLOPE32 * x, x)
+        scale, rounds = np.where(neg, SLOPE32, 1.0), rounds + neg
+    if s.get("mask") is not None:
+        assert epi == EPI_STORE, "launch_gemm refuses a mask with an accumulate"
+        g = np.where(np.asarray(s["mask"], np.float32)[:M, :N] > 0, 1.0, SLOPE32)
+        x, scale, rounds = x * g, scale * g, rounds + (g != 1.0)
+    if exact and epi == EPI_STORE:
+        # an exact sum times 0.01f rounds once: float32 of the float64 product, bit for bit
+        rounds = np.where(rounds <= 1, 0, rounds)
+    N1 = s.get("N1", -1)
+    nc = N1 if s.get("c2") is not None else N          # columns that go to c
+    pre = np.asarray(s["c"], np.float64)[dst, :nc] if epi == EPI_ACCUM else np.zeros((M, nc))
+    xc = x[:, :nc] + pre
+    c["want"][dst, :nc] = xc
+    c["bound"][dst, :nc] = (_prod_bound(n + (epi == EPI_ACCUM), K, absprod[:, :nc] * scale[:, :nc],
+                                        absall[:, :nc] * scale[:, :nc] + np.abs(pre), prec, exact) +
+                            rounds[:, :nc] * U24 * np.abs(x[:, :nc]))
+    c["written"][dst, :nc] = True
+    out["c"] = c
+    if s.get("c2") is not None:
+        c2 = blank("c2")
+        c2["want"][:M, :N - N1] = x[:, N1:]
+        c2["bound"][:M, :N - N1] = (_prod_bound(n, K, absprod[:, N1:] * scale[:, N1:], absall[:, N1:] * scale[:, N1:],
+                                                prec, exact) + rounds[:, N1:] * U24 * np.abs(x[:, N1:]))
+        c2["written"][:M, :N - N1] = True
+        out["c2"] = c2
+    return out
+
+
+def bits32(a):
+    return np.ascontiguousarray(a, np.float32).view(np.uint32)
+
+
+def check_written(name, got, pre, ref, exact=False):
+    """One output buffer of a launch against its reference entry (want, bound,
+    written): an element the launch may not write must hold the pre-fill bit
+    for bit; a written one must lie within its bound of want -- or, exact,
+    hold float32(want) bit for bit (exact-sum inputs; a bound that is not 0
+    there, the L2 norm's own roundings, is still applied as a bound).  Raises
+    naming buffer, row and column; returns the largest error / bound."""
+    got, pre = np.asarray(got, np.float32), np.asarray(pre, np.float32)
+    sh = ref["written"].shape
+    assert got.shape == sh and pre.shape == sh, (name, got.shape, pre.shape, sh)
+    g2, p2, w2 = (np.reshape(v, (sh[0], -1)) for v in (got, pre, ref["written"]))
+    where = lambda i: f"buffer {name}, row {i[0]}, column {i[1]}"
+    stray = np.argwhere((bits32(g2) != bits32(p2)) & ~w2)
+    if len(stray):
+        i = tuple(int(v) for v in stray[0])
+        raise AssertionError(f"{where(i)}: {len(stray)} elements outside the launch's outputs changed, first "
+                             f"{p2[i]!r} (bits {bits32(p2)[i]:#010x}) -> {g2[i]!r}")
+    want, bound = np.reshape(ref["want"], g2.shape), np.reshape(ref["bound"], g2.shape)
+    if exact:
+        tight = w2 & (bound == 0)
+        w32 = np.where(tight, want, 0.0).astype(np.float32)
+        bad = np.argwhere(tight & (bits32(g2) != bits32(w32)))
+        if len(bad):
+            i = tuple(int(v) for v in bad[0])
+            raise AssertionError(f"{where(i)}: {len(bad)} elements differ from the exact result, first got "
+                                 f"{g2[i]!r}, float64 gives {want[i]!r}")
+        w2 = w2 & ~tight                               # (checked; float32(want) need not equal want)
+    err = np.abs(g2.astype(np.float64) - np.where(w2, want, 0.0))
+    err = np.where(w2, np.where(np.isnan(err), np.inf, err), 0.0)
+    return _first_bad(f"buffer {name}", err, np.where(w2, bound, 0.0), lambda i: f"row {i[0]}, column {i[1]}")
+
+
+def check_gemm_form(got, pre, ref, exact=False):
+    """every output buffer of a launch (dicts by buffer name); returns the
+    largest error / bound over them"""
+    assert set(got) == set(ref), (sorted(got), sorted(ref))
+    return max(check_written(k, got[k], pre[k], ref[k], exact) for k in sorted(ref))
+
+
+def apply_launch(pre, ref):
+    """what a correct launch leaves: float32(want) where written, the pre-fill
+    elsewhere (the host tests plant their defects into this)"""
+    return {k: np.where(ref[k]["written"], np.nan_to_num(ref[k]["want"]), np.asarray(pre[k], np.float32))
+            .astype(np.float32) for k in ref}
+
+
+def exact_ints(rng, shape, lim=8):
+    """integers of magnitude <= lim as float32: exact in a bf16 hi plane, sums
+    of up to 2^24 / lim^2 products exact in float32"""
+    return rng.integers(-lim, lim + 1, shape).astype(np.float32)
+
+
+def wide_rows(rng, shape):
+    """Gaussians with a wide-range row scaling 2^(-20 .. 19), as
+    test_split_bf16_products_are_fp32_accurate scales its rows"""
+    x = rng.standard_normal(shape)
+    return (x * np.exp2(rng.integers(-20, 20, (shape[0],) + (1,) * (len(shape) - 1)))).astype(np.float32)
+
+
+def form_values(rng, shape, exact, wide=False):
+    """a case's inputs: exact-sum integers, or Gaussians (wide: row-scaled)"""
+    if exact:
+        return exact_ints(rng, shape)
+    return wide_rows(rng, shape) if wide else rng.standard_normal(shape).astype(np.float32)
+
+
+# ---- reduce_slabs_2d_kernel
+def reduce_slabs32(part):
+    """reduce_slabs_2d_kernel's additions in numpy float32, part [S][...]:
+    group g = 0..3 sums slabs g, g + 4, ...: while k + 12 < S, acc += (x[k] +
+    x[k + 4]) + (x[k + 8] + x[k + 12]) and k += 16; then acc += x[k], k += 4;
+    the result is (acc0 + acc1) + (acc2 + acc3)"""
+    x = np.asarray(part, np.float32)
+    S = x.shape[0]
+    acc = []
+    for g in range(4):
+        a = np.zeros(x.shape[1:], np.float32)
+        k = g
+        while k + 12 < S:
+            a = a + ((x[k] + x[k + 4]) + (x[k + 8] + x[k + 12]))
+            k += 16
+        while k < S:
+            a = a + x[k]
+            k += 4
+        acc.append(a)
+    return (acc[0] + acc[1]) + (acc[2] + acc[3])
+
+
+def reduce_bias32(bpart):
+    """the bias blocks of the same kernel: group g adds bpart[g], bpart[g + 4],
+    ... one by one; (acc0 + acc1) + (acc2 + acc3)"""
+    x = np.asarray(bpart, np.float32)
+    acc = []
+    for g in range(4):
+        a = np.zeros(x.shape[1:], np.float32)
+        for k in range(g, x.shape[0], 4):
+            a = a + x[k]
+        acc.append(a)
+    return (acc[0] + acc[1]) + (acc[2] + acc[3])
+
+
+def check_reduce_slabs(name, got_full, pre_full, part, M, N, emul=reduce_slabs32):
+    """out [M][ld] of the reduction of part [S][M][N]: columns < N bitwise the
+    order emulation and within (S + 1) 2^-24 sum_s |part| of the float64 sum (S
+    terms pass through at most S - 1 additions; the + 1 is gemm_bound's slack
+    scaled down to a sum without products); columns >= N and rows >= M keep
+    the pre-fill.  Returns error / bound against float64."""
+    part = np.asarray(part, np.float32)
+    S = part.shape[0]
+    p64 = part.astype(np.float64)
+    ref = dict(want=np.full(np.shape(pre_full), np.nan), bound=np.zeros(np.shape(pre_full)),
+               written=np.zeros(np.shape(pre_full), bool))
+    sl = (slice(0, M), slice(0, N)) if ref["want"].ndim == 2 else (slice(0, M),)
+    ref["want"][sl], ref["bound"][sl], ref["written"][sl] = p64.sum(0), (S + 1) * U24 * np.abs(p64).sum(0), True
+    worst = check_written(name, got_full, pre_full, ref)
+    em = dict(ref, want=np.array(ref["want"]), bound=np.zeros_like(ref["bound"]))
+    em["want"][sl] = emul(part)
+    check_written(name + " (order emulation)", got_full, pre_full, em, exact=True)
+    return worst
+
+
+# ---- Adam
+def adam_coef(step, lr=1e-3, beta1=0.9, beta2=0.999):
+    """the host's coef (pinsage_training._adam_coef): formed in double, staged as float32"""
+    return np.array([lr / (1 - beta1 ** step), (1 - beta2 ** step) ** 0.5], np.float32)
+
+
+def adam_reference(p, g, m, v, coef, beta1=0.9, beta2=0.999, eps=1e-8, swap_betas=False, drop_bc2=False):
+    """One step of torch's _single_tensor_adam in float64 from float32 state,
+    with the step size and sqrt(1 - beta2^t) the host staged (coef, float32):
+        m' = lerp(m, g, 1 - beta1);  v' = beta2 v + (1 - beta2) g^2
+        p' = p - coef[0] m' / (sqrt(v') / coef[1] + eps)
+    and the bound of adam1's float32 evaluation (conv.hip), u = 2^-24, every
+    rounding <= u |result| or half a denormal step (TINY32):
+      m'  4 roundings -- g - m, (float)(1 - beta1), their product, the sum:
+          E_m = u (3 (1 - beta1) |g - m| + |m'|) + 3 TINY32
+      v'  beta2 v: (float)beta2 and the product; (1 - beta2) g g: the
+          constant and two products; the sum: every term is >= 0, so
+          E_v = 4 u v' + 4 TINY32 (g^2 of a tiny g underflows to 0)
+      p'  s = sqrt(v'): |sqrt a - sqrt b| <= min(sqrt |a - b|, |a - b| / sqrt b),
+          plus the root's rounding; den = s / bc2 + eps rounds three times (the
+          quotient, (float)eps, the sum); q = m' / den once; coef[0] q once;
+          p - coef[0] q once:
+          E_den = E_s / bc2 + 3 u den,  E_q = E_m / den + |m'| E_den / den^2 + u |q|,
+          E_p = coef[0] (E_q + u |q|) + u |p'| + TINY32
+    (first order; the 1 + 2^-10 factor carries the second-order terms, u^2
+    relative).  swap_betas / drop_bc2: the planted defects of the host tests.
+    Returns dict(p, m, v, E_p, E_m, E_v)."""
+    p, g, m, v = (np.asarray(a, np.float32).astype(np.float64) for a in (p, g, m, v))
+    ss, bc2 = float(coef[0]), float(coef[1])
+    if swap_betas:
+        beta1, beta2 = beta2, beta1
+    if drop_bc2:
+        bc2 = 1.0
+    m1 = m + (g - m) * (1 - beta1)
+    v1 = v * beta2 + (1 - beta2) * g * g
+    s = np.sqrt(v1)
+    den = s / bc2 + eps
+    q = m1 / den
+    p1 = p - ss * q
+    E_m = U24 * (3 * (1 - beta1) * np.abs(g - m) + np.abs(m1)) + 3 * TINY32
+    E_v = 4 * U24 * v1 + 4 * TINY32
+    with np.errstate(divide="ignore", invalid="ignore"):
+        E_s = np.minimum(np.sqrt(E_v), np.where(s > 0, E_v / np.where(s > 0, s, 1.0), np.inf)) + U24 * s
+    E_den = E_s / bc2 + 3 * U24 * den
+    E_q = E_m / den + np.abs(m1) * E_den / den ** 2 + U24 * np.abs(q)
+    E_p = ss * (E_q + U24 * np.abs(q)) + U24 * np.abs(p1) + TINY32
+    f = 1 + 2.0 ** -10
+    return dict(p=p1, m=m1, v=v1, E_p=f * E_p, E_m=f * E_m, E_v=f * E_v)
+
+
+def check_adam(got_p, got_m, got_v, ref, where=lambda i: f"element {i[0]}"):
+    """p, m, v after a step against adam_reference; names the buffer and the
+    element.  Returns the largest error / bound."""
+    worst = 0.0
+    for name, got in (("m", got_m), ("v", got_v), ("p", got_p)):
+        err = np.abs(np.asarray(got, np.float64) - ref[name])
+        err = np.where(np.isnan(err), np.inf, err)
+        worst = max(worst, _first_bad(f"adam {name}", err, ref["E_" + name], where))
+    return worst
+
+
+def adam_gradient(rng, n):
+    """gradient elements that are exactly 0, 1e-30 (sqrt(v) / bc2 far below
+    eps), near 1e4, and Gaussians, in every position mod 4"""
+    g = rng.standard_normal(n).astype(np.float32)
+    for k, val in enumerate((0.0, 1e-30, 1e4, -9.7e3, -1e-30)):
+        g[k::7][: max(1, n // 11)] = val
+    return g
+
+
+# ---- norm_lrelu_bwd
+def norm_lrelu_bwd_reference(y, nrm, dy):
+    """dp = lrelu'(y) (dy - y (y . dy)) / nrm in float64 (y == 0 takes the
+    slope) and its float32 bound, carried as head_reference_bwd carries dp's:
+    the dot product of `out` terms within (out + 4) u sum |y dy|, then the
+    product y dot, the subtraction, 1 / nrm, and the two scalings round once
+    each: (|y| E_dot + 5 u (|dy| + |y dot|)) lrelu' / nrm."""
+    y, nrm, dy = (np.asarray(a, np.float64) for a in (y, nrm, dy))
+    o = y.shape[1]
+    dot = (y * dy).sum(1, keepdims=True)
+    E_dot = gemm_bound(o, np.abs(y * dy).sum(1, keepdims=True))
+    sy = np.where(y > 0, 1.0, SLOPE32)
+    return (sy * (dy - y * dot) / nrm[:, None],
+            sy * (np.abs(y) * E_dot + 5 * U24 * (np.abs(dy) + np.abs(y * dot))) / nrm[:, None])

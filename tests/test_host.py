@@ -844,3 +844,221 @@ def test_head_checkers_reject_single_defects():
                                 G1w, G2w, dP1)
     for got, want in ((d64["dp"], pre.grad), (d64["dG2"], G2t.grad), (d64["dG1"], G1t.grad), (d64["db1"], b1t.grad)):
         assert np.abs(got - want.numpy()).max() <= 1e-12 * np.abs(want.numpy()).max()
+
+
+# ----------------------------------------------------------------------------- GEMM forms, slab reduction, Adam
+# The references and checkers of tests/test_gpu_gemm_forms.py and
+# tests/test_gpu_optimizer.py: pinned to an independent restatement (plain
+# loops, torch.optim.Adam), and each planted defect rejected with its location.
+def _form_spec(rng, epi=0, exact=True, **kw):
+    import parity_util as pu
+    M, N, K, K1 = 7, 12, 24, 8
+    fv = lambda *sh: pu.form_values(rng, sh, exact)
+    s = dict(M=M, N=N, K=K, a=fv(11, K1 + 4), a_idx=rng.permutation(11)[:M], K1=K1, a2=fv(9, K - K1 + 4),
+             a2_idx=rng.permutation(9)[:M], b=fv(N, K + 4), bias=fv(N), epi=epi,
+             c=fv(M + 4, N + 3) if epi == pu.EPI_ACCUM else np.full((M + 4, N + 3), np.nan, np.float32),
+             c_idx=rng.permutation(M + 4)[:M])
+    s.update(kw)
+    return s
+
+
+def test_gemm_form_reference_against_plain_loops():
+    import parity_util as pu
+    rng = np.random.default_rng(0)
+    s = _form_spec(rng, epi=pu.EPI_ACCUM, exact=False, act=True, N1=8, c2=np.full((9, 6), np.nan, np.float32))
+    ref = pu.gemm_form_reference(s)
+    slope = float(np.float32(0.01))
+    seen_c, seen_c2 = np.zeros(s["c"].shape, bool), np.zeros(s["c2"].shape, bool)
+    for m in range(s["M"]):
+        for n in range(s["N"]):
+            x = float(s["bias"][n])
+            for k in range(s["K"]):
+                a = s["a"][s["a_idx"][m], k] if k < s["K1"] else s["a2"][s["a2_idx"][m], k - s["K1"]]
+                x += float(a) * float(s["b"][n, k])
+            x = x if x > 0 else slope * x
+            if n < s["N1"]:
+                r = s["c_idx"][m]
+                assert abs(ref["c"]["want"][r, n] - (x + float(s["c"][r, n]))) < 1e-12
+                seen_c[r, n] = True
+            else:
+                assert abs(ref["c2"]["want"][m, n - s["N1"]] - x) < 1e-12
+                seen_c2[m, n - s["N1"]] = True
+    assert (ref["c"]["written"] == seen_c).all() and (ref["c2"]["written"] == seen_c2).all()
+    # M-major A, N-major B in two segments gathered by k, partial slabs with the column sums of A
+    K, M, N, N1, S = 70, 8, 12, 4, 4
+    b_idx = rng.integers(0, K + 3, K)
+    p = dict(M=M, N=N, K=K, a_kmajor=False, b_kmajor=False, a=rng.standard_normal((K, M + 4)), N1=N1, b_idx=b_idx,
+             b=rng.standard_normal((K + 3, N1 + 4)), b2=rng.standard_normal((K, N - N1)), epi=pu.EPI_PARTIAL, splits=S,
+             c=np.full((S * M + 1, N), np.nan, np.float32), bias_part=np.full((S + 1, M), np.nan, np.float32))
+    ref = pu.gemm_form_reference(p)
+    for sp, (k0, k1) in enumerate(((0, 32), (32, 64), (64, 70), (70, 70))):   # ceil(70 / 4) = 18 -> chunks of 32
+        for m in range(M):
+            assert abs(ref["bias_part"]["want"][sp, m] - p["a"][k0:k1, m].sum()) < 1e-12
+            for n in range(N):
+                want = sum(p["a"][k, m] * (p["b"][b_idx[k], n] if n < N1 else p["b2"][k, n - N1]) for k in range(k0, k1))
+                assert abs(ref["c"]["want"][sp * M + m, n] - want) < 1e-12
+    assert ref["c"]["written"][:S * M].all() and not ref["c"]["written"][S * M:].any()
+    assert ref["bias_part"]["written"][:S].all() and not ref["bias_part"]["written"][S:].any()
+    assert (ref["c"]["want"][3 * M:4 * M] == 0).all()       # the empty split: zeros, written
+
+
+def _at(buffer, row, col=None):
+    """the location as either checker message states it"""
+    return rf"buffer {buffer}\b.*row {row}, column" + ("" if col is None else rf" {col}\b")
+
+
+def _rejects(got, pre, ref, text, exact=True):
+    import parity_util as pu
+    pu.check_gemm_form(pu.apply_launch(pre, ref), pre, ref, exact)   # (the unplanted result passes)
+    with pytest.raises(AssertionError, match=text):
+        pu.check_gemm_form(got, pre, ref, exact)
+
+
+def test_gemm_form_checker_rejects_planted_defects():
+    import parity_util as pu
+    rng = np.random.default_rng(1)
+    for exact in (True, False):
+        # a segment boundary off by one k: column K1 of row 2 read from the first segment
+        s = _form_spec(rng, exact=exact)
+        pre, ref = {"c": s["c"]}, pu.gemm_form_reference(s, 0, exact)
+        A, B = pu.gemm_operands(s)
+        got = pu.apply_launch(pre, ref)
+        r = s["c_idx"][2]
+        got["c"][r, :12] += ((float(s["a"][s["a_idx"][2], 8]) - A[2, 8]) * B[8]).astype(np.float32)
+        assert s["a"][s["a_idx"][2], 8] != A[2, 8] and B[8, 0] != 0
+        _rejects(got, pre, ref, _at("c", r, 0), exact)
+        # a scatter row swapped
+        got = pu.apply_launch(pre, ref)
+        r0, r1 = sorted(s["c_idx"][:2])
+        got["c"][[r0, r1]] = got["c"][[r1, r0]]
+        _rejects(got, pre, ref, _at("c", r0), exact)
+        # a store one row past M (into a row no c_idx names), one column past N
+        free = sorted(set(range(s["c"].shape[0])) - set(s["c_idx"].tolist()))[0]
+        got = pu.apply_launch(pre, ref)
+        got["c"][free, 3] = 1.0
+        _rejects(got, pre, ref, _at("c", free, 3), exact)
+        got = pu.apply_launch(pre, ref)
+        got["c"][s["c_idx"][4], 12] = got["c"][s["c_idx"][4], 11]
+        _rejects(got, pre, ref, _at("c", s['c_idx'][4], 12), exact)
+        # an accumulate that dropped its pre-value
+        s = _form_spec(rng, epi=pu.EPI_ACCUM, exact=exact)
+        r = s["c_idx"][5]
+        s["c"][r, 7] = 3.0
+        pre, ref = {"c": s["c"]}, pu.gemm_form_reference(s, 0, exact)
+        got = pu.apply_launch(pre, ref)
+        got["c"][r, 7] -= 3.0
+        _rejects(got, pre, ref, _at("c", r, 7), exact)
+        # a store one row past M into the split output
+        s = _form_spec(rng, exact=exact, N1=4, c2=np.full((9, 10), np.nan, np.float32))
+        pre, ref = {"c": s["c"], "c2": s["c2"]}, pu.gemm_form_reference(s, 0, exact)
+        got = pu.apply_launch(pre, ref)
+        got["c2"][7, 0] = got["c2"][6, 0]
+        _rejects(got, pre, ref, _at("c2", 7, 0), exact)
+        # the mask's slope the wrong way at x == 0
+        mask = rng.standard_normal((7, 16)).astype(np.float32)
+        mask[1, 2], mask[1, 3] = 0.0, -0.0
+        s = _form_spec(rng, exact=exact, mask=mask, c_idx=None)
+        pre, ref = {"c": s["c"]}, pu.gemm_form_reference(s, 0, exact)
+        A, B = pu.gemm_operands(s)
+        for col in (2, 3):
+            got = pu.apply_launch(pre, ref)
+            got["c"][1, col] = np.float32(A[1] @ B[:, col] + s["bias"][col])
+            assert got["c"][1, col] != 0
+            _rejects(got, pre, ref, _at("c", 1, col), exact)
+    # the L2-norm epilogue: a norm and an element a few ulps off are rejected, the rounded result passes
+    s = _form_spec(rng, epi=pu.EPI_L2NORM, exact=False, norms=np.full(9, np.nan, np.float32))
+    pre, ref = {"c": s["c"], "norms": s["norms"]}, pu.gemm_form_reference(s)
+    got = pu.apply_launch(pre, ref)
+    got["norms"][3] *= np.float32(1 + 1e-4)
+    _rejects(got, pre, ref, _at("norms", 3, 0), False)
+    got = pu.apply_launch(pre, ref)
+    got["norms"][7] = 1.0
+    _rejects(got, pre, ref, _at("norms", 7, 0), False)
+
+
+def test_reduce_slabs_order_emulation_and_checker():
+    import parity_util as pu
+    rng = np.random.default_rng(2)
+    f = np.float32
+    for S in (1, 2, 3, 4, 5, 16, 17, 64):
+        x = rng.standard_normal((S, 3, 8)).astype(f)
+        # group g by hand: the first sixteen slabs four at a time, then one by one
+        acc = []
+        for g in range(4):
+            ks = list(range(g, S, 4))
+            a = np.zeros((3, 8), f)
+            while len(ks) >= 4:
+                a = a + ((x[ks[0]] + x[ks[1]]) + (x[ks[2]] + x[ks[3]]))
+                ks = ks[4:]
+            for k in ks:
+                a = a + x[k]
+            acc.append(a)
+        want = (acc[0] + acc[1]) + (acc[2] + acc[3])
+        assert (pu.bits32(pu.reduce_slabs32(x)) == pu.bits32(want)).all(), S
+        pre = np.full((5, 12), np.nan, f)
+        good = pre.copy()
+        good[:3, :8] = want
+        pu.check_reduce_slabs("out", good, pre, x, 3, 8)
+        if S >= 2:   # a slab skipped
+            bad = pre.copy()
+            bad[:3, :8] = pu.reduce_slabs32(np.delete(x, S // 2, 0))
+            with pytest.raises(AssertionError, match="buffer out.*row 0, column 0"):
+                pu.check_reduce_slabs("out", bad, pre, x, 3, 8)
+        bad = good.copy()
+        bad[3, 0] = 0.0      # a store one row past M
+        with pytest.raises(AssertionError, match=_at("out", 3, 0)):
+            pu.check_reduce_slabs("out", bad, pre, x, 3, 8)
+    ints = pu.exact_ints(rng, (17, 3, 8))
+    assert (pu.reduce_slabs32(ints) == ints.astype(np.float64).sum(0)).all()
+
+
+def test_adam_reference_is_torch_adam_and_checker_rejects_defects():
+    import parity_util as pu
+    rng = np.random.default_rng(3)
+    n, lr, betas, eps = 64, 1e-3, (0.9, 0.999), 1e-8
+    p0 = rng.standard_normal(n).astype(np.float32)
+    # one step from float32 state against torch, exactly the restated formulas
+    tp = torch.nn.Parameter(torch.from_numpy(p0.astype(np.float64)))
+    opt = torch.optim.Adam([tp], lr=lr, betas=betas, eps=eps)
+    g = pu.adam_gradient(rng, n)
+    tp.grad = torch.from_numpy(g.astype(np.float64))
+    opt.step()
+    c1 = np.array([lr / (1 - betas[0]), (1 - betas[1]) ** 0.5])
+    r = pu.adam_reference(p0, g, np.zeros(n, np.float32), np.zeros(n, np.float32), c1, *betas, eps)
+    assert np.abs(r["p"] - tp.detach().numpy()).max() <= 1e-12
+    st = opt.state[tp]
+    assert np.abs(r["m"] - st["exp_avg"].numpy()).max() <= 1e-15 * 1e4
+    assert np.abs(r["v"] - st["exp_avg_sq"].numpy()).max() <= 1e-15 * 1e8
+    # the checker: the float32 rounding of the reference passes; swapped betas and a dropped bias correction do not
+    m0 = (0.1 * rng.standard_normal(n)).astype(np.float32)
+    v0 = (rng.random(n) * 1e-2).astype(np.float32)
+    coef = pu.adam_coef(3, lr, *betas)
+    ref = pu.adam_reference(p0, g, m0, v0, coef, *betas, eps)
+    f = lambda d: (d["p"].astype(np.float32), d["m"].astype(np.float32), d["v"].astype(np.float32))
+    pu.check_adam(*f(ref), ref)
+    with pytest.raises(AssertionError, match="adam m: .* element 0"):
+        pu.check_adam(*f(pu.adam_reference(p0, g, m0, v0, coef, *betas, eps, swap_betas=True)), ref)
+    bad = pu.adam_reference(p0, g, m0, v0, coef, *betas, eps, drop_bc2=True)
+    assert (bad["m"] == ref["m"]).all() and (bad["v"] == ref["v"]).all()
+    with pytest.raises(AssertionError, match="adam p: .* element"):
+        pu.check_adam(*f(bad), ref)
+    # a refused step's state and the tiny gradients: g = 1e-30 leaves v's float32 at 0 within the bound
+    z = np.zeros(4, np.float32)
+    tiny = pu.adam_reference(z, np.full(4, 1e-30, np.float32), z, z, pu.adam_coef(1), *betas, eps)
+    pu.check_adam(tiny["p"].astype(np.float32), tiny["m"].astype(np.float32), z, tiny)
+
+
+def test_norm_lrelu_bwd_reference_is_autograd():
+    import parity_util as pu
+    rng = np.random.default_rng(4)
+    x = torch.from_numpy(rng.standard_normal((5, 9))).requires_grad_()
+    x.data[0, 0] = 0.0
+    v = torch.nn.functional.leaky_relu(x)
+    nrm = v.norm(dim=1)
+    y = v / nrm[:, None]
+    dy = rng.standard_normal((5, 9))
+    y.backward(torch.from_numpy(dy))
+    want, bound = pu.norm_lrelu_bwd_reference(y.detach().numpy(), nrm.detach().numpy(), dy)
+    # (0.01f against 0.01: 2.2e-8 relative in the slope's rows)
+    assert np.abs(want - x.grad.numpy()).max() <= 1e-7 * np.abs(want).max()
+    assert (bound > 0).all()
