@@ -7,71 +7,23 @@
 #include <string>
 #include <vector>
 
-#include "aggw.h"
 #include "../../include/pinsage_hip.h"
-#include "common.h"
+#include "aggw.h"
+#include "capi.h"
+#include "conv.h"
+#include "fly.h"
+#include "frontier.h"
 #include "gemm.h"
+#include "knn.h"
+#include "ppr_topk.h"
+#include "sampler.h"
 #include "wgrad.h"
-#include "mt19937.h"
 
 namespace ps {
 
 static thread_local std::string g_err;
 void set_error(const std::string& msg) { g_err = msg; }
 const char* last_error() { return g_err.c_str(); }
-
-int launch_mt_expand(const MTChunk*, int64_t, int64_t, int64_t, uint32_t*, hipStream_t);
-int launch_walk(const int64_t*, const int32_t*, const int64_t*, int64_t, int64_t, float,
-                const uint32_t*, uint64_t, uint32_t, int64_t, int32_t*, int*, hipStream_t);
-int launch_visit_topk(const int32_t*, const int64_t*, int64_t, int64_t, int64_t, int64_t, void*,
-                      double*, int64_t*, float*, int32_t*, int64_t, hipStream_t);
-int launch_visit_dense(const int32_t*, const int64_t*, int64_t, int64_t, int64_t, double*,
-                       hipStream_t);
-int64_t fly_workspace_bytes(int64_t, int64_t, int64_t, int64_t, int64_t);
-int fly_init_workspace(void*, int64_t, int64_t, int64_t, int64_t, int64_t, hipStream_t);
-int fly_publish_err(const int*, void*, int64_t, int64_t, const int64_t*, int64_t, hipStream_t);
-int fly_gate_adam(int*, float*, hipStream_t);
-int fly_sample(const int64_t*, const int32_t*, int64_t, const int64_t*, int64_t, int64_t, int64_t, int64_t, int64_t,
-               float, const uint64_t*, void*, int64_t, int32_t* const*, float* const*, int32_t**, int64_t, int64_t*,
-               int*, int64_t*, int64_t, const float*, int64_t, int64_t, float*, int64_t, int*, hipStream_t);
-int launch_walk_runs(const int64_t*, const int32_t*, const int64_t*, int64_t, int, float,
-                     const uint32_t*, uint64_t, uint32_t, int64_t, uint2*, int*, int*, hipStream_t);
-int launch_heap_topk(const uint2*, const int*, int64_t, int, int, double*, int64_t*, float*, int32_t*,
-                     int, hipStream_t, const int* n_src_dev = nullptr);
-int64_t bitset_words(int64_t universe);
-int64_t bitset_blocks(int64_t universe);
-int launch_mark_i64(unsigned long long*, const int64_t*, int64_t, int64_t, int*, hipStream_t);
-int launch_mark_table_i64(unsigned long long*, const int64_t*, int64_t, const int32_t*, int64_t,
-                          int, int64_t, int*, hipStream_t);
-int64_t triplet_loss_scratch_bytes(int64_t B, int64_t d);
-int launch_triplet_loss(const float* Z, int B, int d, float margin, float* G, void* scratch, float* scal,
-                        hipStream_t st);
-int launch_set_finalize(unsigned long long*, const unsigned long long*, const unsigned long long*,
-                        int64_t, uint32_t*, uint32_t*, int32_t*, int*, hipStream_t);
-int launch_agg(const float*, int, const int32_t*, const float*, int, const int*, int64_t, float*,
-               hipStream_t);
-int launch_gather_rows(const float*, int64_t, int64_t, int, const int64_t*, int64_t, float*, int64_t,
-                       hipStream_t);
-int launch_l2norm_rows(float* y, int64_t n, int out, float* norms, hipStream_t st);
-int launch_set_rank_table(const int64_t*, int64_t, const int32_t*, int64_t, int, const unsigned long long*,
-                          const uint32_t*, int32_t*, hipStream_t);
-int launch_norm_lrelu_bwd(const float*, const float*, const float*, int, const int*, int64_t, float*, float*,
-                          int, const int*, int*, int64_t, hipStream_t);
-int launch_adam(float*, const float*, float*, float*, int64_t, const float*, double, double, float, hipStream_t);
-int launch_reduce_slabs_2d(const float*, int, int64_t, int, int, float*, int64_t, const float*, float*,
-                           const AdamSlice*, hipStream_t);
-int csr_prepare();
-int launch_csr_build(const int32_t*, const float*, const int*, int64_t, int, const int*, int64_t, int*, int*,
-                     int*, int*, int*, int2*, int2*, int*, int2*, int*, float*, int, hipStream_t, int2*);
-int64_t dq_chunk_capacity(int64_t, int, int64_t);
-int64_t dq_split_capacity(int64_t, int);
-int dq_tree_levels(int64_t max_chunks);
-int launch_dq_chunks(const int2*, const int*, int64_t, const int2*, const int*, int64_t, const int*,
-                     const int2*, const float*, int64_t, const float*, int, float*, float*, hipStream_t,
-                     const int32_t*, int32_t*, const int*, int*, uint16_t*, int64_t);
-int64_t knn_scratch_bytes(int64_t, int64_t);
-int launch_knn_cosine(const float*, int64_t, int64_t, int64_t, const int64_t*, int64_t, int64_t,
-                      float, void*, int64_t, float*, int64_t*, int*, hipStream_t);
 
 // Fisher-Yates prefix of torch.randperm(n): first k entries, all n-1 draws consumed.
 // Only the <= 2k positions the first k swaps touch are stored (open addressing).
@@ -106,8 +58,6 @@ static void randperm_prefix(MTState& g, int64_t n, int64_t k, int64_t* out) {
   if (n - 1 > steps) g.skip(n - 1 - steps);
 }
 
-// sample_batch with easy negatives (pinsage_training.py:53-77, 89-97); shared
-// with the batch sampler runtime (loader.hip)
 int sample_batch_easy(MTState& g, const int64_t* positives, int64_t P, int64_t n_items,
                       int64_t batch_size, int64_t* batch_out, int64_t* nodeset_out,
                       int64_t* n_nodeset) {
@@ -865,14 +815,49 @@ int pinsage_agg_transpose(const int32_t* loc, const float* w, const int* n_rows_
   auto at_2 = [sc](int64_t o) { return reinterpret_cast<int2*>(sc + o); };
   hipStream_t st = (hipStream_t)stream;
   PS_TRY(csr_prepare());
-  PS_TRY(launch_csr_build(loc, w, n_rows_dev, n_rows_max, (int)T, n_q_dev, n_q_max, at_i(a.cnt), at_i(a.bsum),
-                          at_i(a.off), at_i(a.cursor), at_i(a.cbase), at_2(a.occ2), at_2(a.chunks),
-                          at_i(a.nchunks), at_2(a.split), at_i(a.nsplit), dpq, (int)hid, st, at_2(a.occ2b)));
-  return launch_dq_chunks(at_2(a.chunks), at_i(a.nchunks), a.max_chunks, at_2(a.split), at_i(a.nsplit),
-                          a.max_split, at_i(a.off), at_2(a.occ2), dagg, ld_dagg, q, (int)hid, dpq,
-                          reinterpret_cast<float*>(sc + a.part), st, nullptr, nullptr,
-                          mode == 1 ? at_i(a.cbase) : nullptr, mode == 1 ? at_i(a.tk) : nullptr, dpq_planes,
-                          plane_stride);
+  CsrBuildParams cb;
+  cb.loc = loc;
+  cb.wloc = w;
+  cb.nS = n_rows_dev;
+  cb.S_max = n_rows_max;
+  cb.T = (int)T;
+  cb.nN = n_q_dev;
+  cb.N_max = n_q_max;
+  cb.hid = (int)hid;
+  cb.cnt = at_i(a.cnt);
+  cb.bsum = at_i(a.bsum);
+  cb.off = at_i(a.off);
+  cb.cursor = at_i(a.cursor);
+  cb.cbase = at_i(a.cbase);
+  cb.occ2 = at_2(a.occ2);
+  cb.chunks = at_2(a.chunks);
+  cb.nchunks = at_i(a.nchunks);
+  cb.split = at_2(a.split);
+  cb.nsplit = at_i(a.nsplit);
+  cb.occ2_tmp = at_2(a.occ2b);
+  PS_TRY(launch_csr_build(cb, st));
+  DqChunkParams dq;
+  dq.chunks = cb.chunks;
+  dq.nchunks = cb.nchunks;
+  dq.max_chunks = a.max_chunks;
+  dq.split = cb.split;
+  dq.nsplit = cb.nsplit;
+  dq.max_split = a.max_split;
+  dq.off = cb.off;
+  dq.occ2 = cb.occ2;
+  dq.dagg = dagg;
+  dq.ld_dagg = ld_dagg;
+  dq.q = q;
+  dq.hid = (int)hid;
+  dq.dpq = dpq;
+  dq.part = reinterpret_cast<float*>(sc + a.part);
+  if (mode == 1) {
+    dq.cbase = cb.cbase;
+    dq.tk = at_i(a.tk);
+  }
+  dq.dpq3 = dpq_planes;
+  dq.ps3 = plane_stride;
+  return launch_dq_chunks(dq, st);
 }
 
 int64_t pinsage_fly_workspace_bytes(int64_t n, int64_t B, int64_t n_layers, int64_t T, int64_t n_hops) {

@@ -45,4 +45,171 @@ struct LayerPreps {
 // every layer's tables in one launch (S_max / N_max: the sets' capacities)
 int launch_layer_preps(const LayerPrep* p, const int64_t* S_max, const int64_t* N_max, int n, int T, hipStream_t st);
 
+// In-place row L2 normalisation of y [n][out]; norms[r] = ||y_r|| (nullable).
+int launch_l2norm_rows(float* y, int64_t n, int out, float* norms, hipStream_t st);
+
+// The n batch positions grouped by their top-set rank (pos_rank), in position
+// order: pos_sorted[rank_off[r] .. rank_off[r + 1]) for every rank r <= *nS.
+int launch_pos_csr(const int32_t* pos_rank, int64_t n, const int* nS, int* rank_off, int32_t* pos_sorted,
+                   hipStream_t st);
+
+// out[i] = Z[pr[i]] for the n positions (rows of d floats)
+int launch_gather_out(const float* Z, int d, const int32_t* pr, int64_t n, float* out, hipStream_t st);
+
+// out[i] (row stride ldo) = h[idx[i]] (row stride ldh, n_h rows of d floats), i < n
+int launch_gather_rows(const float* h, int64_t ldh, int64_t n_h, int d, const int64_t* idx, int64_t n,
+                       float* out, int64_t ldo, hipStream_t st);
+
+// autograd: the output rows' cotangents go into the loss's accumulators (G slab
+// 0, K slab 0); dZ = K * G is formed by the fused head backward (or here, for
+// the unfused head: scale = true)
+int launch_dz_from_dout(const float* dout, int d, const int32_t* pr, int64_t n, const int* nS,
+                        int64_t S_max, float* G, int* Kc, float* dZ, bool scale, const int* rank_off,
+                        const int32_t* pos_sorted, float* Gp, hipStream_t st);
+
+// out[M][N] (row stride ld) = the sum of S slabs part[s] (slab stride `stride`
+// floats), bias_out[M] (nullable) = the sum of bpart[s][M]; adam (nullable):
+// Adam on the slice as it is reduced
+int launch_reduce_slabs_2d(const float* part, int S, int64_t stride, int M, int N, float* out,
+                           int64_t ld, const float* bpart, float* bias_out, const AdamSlice* adam,
+                           hipStream_t st);
+
+// agg[f] = sum_t wloc[f*T+t] * q[loc[f*T+t]] for f < *nS (rows of hid floats)
+int launch_agg(const float* q, int hid, const int32_t* loc, const float* wloc, int T,
+               const int* nS, int64_t S_max, float* agg, hipStream_t st);
+
+// dynamic LDS above 64 KiB must be allowed per kernel (once, outside capture)
+int csr_prepare();
+
+// CSR of the neighbour slots by q row, plus the dq chunk list.  cnt must be
+// zero on entry (zeroed once by pinsage_engine_init_workspace, then left zero
+// by the scan).
+struct CsrBuildParams {
+  const int32_t* loc = nullptr;  // [S][T] q row of every slot (LayerPrep::loc)
+  const float* wloc = nullptr;   // [S][T] the slots' weights
+  const int* nS = nullptr;       // device row count of S (<= S_max)
+  int64_t S_max = 0;
+  int T = 0;
+  const int* nN = nullptr;       // device row count of the q rows (<= N_max)
+  int64_t N_max = 0;
+  int hid = 0;
+  int* cnt = nullptr;            // [N + 1] slots per q row
+  int* bsum = nullptr;           // block sums of the two-launch scan
+  int* off = nullptr;            // [N + 1] out: row starts
+  int* cursor = nullptr;         // [N + 1] fill cursors
+  int* cbase = nullptr;          // [N + 1] out: first chunk of every row
+  int2* occ2 = nullptr;          // out: (source row, weight bits) pairs by q row
+  int2* chunks = nullptr;        // out: the dq chunk list (dq_chunk_capacity entries)
+  int* nchunks = nullptr;
+  int2* split = nullptr;         // out: rows of more than one chunk (dq_split_capacity entries)
+  int* nsplit = nullptr;
+  // set: pairs sorted by source row within a q row (bitwise-reproducible sums);
+  // scratch of occ2's size
+  int2* occ2_tmp = nullptr;
+};
+int launch_csr_build(const CsrBuildParams& p, hipStream_t st);
+
+// upper bound of the dq chunk list: one partial chunk per row plus full ones
+int64_t dq_chunk_capacity(int64_t S_max, int T, int64_t N_max);
+// upper bound of the split-row list: a split row holds more than kDqChunk slots
+int64_t dq_split_capacity(int64_t S_max, int T);
+// levels of the split-row tree for rows of up to max_chunks chunks (fan-in 8)
+int dq_tree_levels(int64_t max_chunks);
+
+// The aggregation's transpose over launch_csr_build's plan: dpq[u] = lrelu'(q[u])
+// * the weighted sum of the dagg rows (row stride ld_dagg) whose slots name q row u.
+struct DqChunkParams {
+  const int2* chunks = nullptr;
+  const int* nchunks = nullptr;
+  int64_t max_chunks = 0;
+  const int2* split = nullptr;
+  const int* nsplit = nullptr;
+  int64_t max_split = 0;
+  const int* off = nullptr;
+  const int2* occ2 = nullptr;
+  const float* dagg = nullptr;
+  int64_t ld_dagg = 0;
+  const float* q = nullptr;
+  int hid = 0;
+  float* dpq = nullptr;
+  float* part = nullptr;  // [max_chunks][hid] chunk partials
+  // chunk rows (csrc set, needs q_src): masked partials stay in part, no
+  // combine; csrc[chunk] = q_src of the chunk's row
+  const int32_t* q_src = nullptr;
+  int32_t* csrc = nullptr;
+  // split-row tree (cbase and tk set, hid <= 512): split rows combined by their
+  // own chunks, no combine launch; tk: dq_tree_levels x max_chunks zeroed ints
+  const int* cbase = nullptr;
+  int* tk = nullptr;
+  // with the tree: dpq also written as hi / mid / lo bf16 planes, plane stride ps3
+  uint16_t* dpq3 = nullptr;
+  int64_t ps3 = 0;
+};
+int launch_dq_chunks(const DqChunkParams& p, hipStream_t st);
+
+// dp = the backward of y = normalize(lrelu(.)) for nrows (device, <= max_rows)
+// rows of n floats; also zeroes z (*z_rows x z_n floats, nullable) and zi
+// (zi_n ints, nullable)
+int launch_norm_lrelu_bwd(const float* y, const float* nrm, const float* dy, int n,
+                          const int* nrows, int64_t max_rows, float* dp, float* z, int z_n,
+                          const int* z_rows, int* zi, int64_t zi_n, hipStream_t st);
+
+// The triplet loss over B triples of Z rows (positions 3b + c -> row
+// pos_rank[3b + c]) and its cotangents per call c in G[c][S_max][d] with the
+// occurrence counts Kc.  G and Kc are zero on entry (init_workspace; then the
+// head backward (or dz_combine) and the first backward kernel leave them zero).
+struct LossParams {
+  const float* Z = nullptr;
+  int d = 0;
+  const int32_t* pos_rank = nullptr;
+  int B = 0;
+  float margin = 0.f;
+  const float* feats = nullptr;  // nullable: the node-feature monitors' table
+  int64_t ld_f = 0;
+  int d_in = 0;
+  const int64_t* batch = nullptr;  // the positions' ids (with feats)
+  float* G = nullptr;
+  int* Kc = nullptr;
+  int64_t S_max = 0;
+  const int* nS = nullptr;
+  float* dZ = nullptr;        // combine_dz: dZ = sum_c K[c] G[c]
+  float* part = nullptr;      // per-block loss partials (launch_loss_monitor)
+  float* colpart = nullptr;   // per-block column sums (the variance monitor)
+  float* hinge = nullptr;     // nullable: [B] per-triple hinge argument (parity tests read it)
+  bool combine_dz = false;
+  // false: the consumer (the fused head backward, head.hip) sums the repeated
+  // ranks' Gp rows itself, in the same order
+  bool rep_sum = false;
+  const int* rank_off = nullptr;  // launch_pos_csr's position CSR
+  const int32_t* pos_sorted = nullptr;
+  float* Gp = nullptr;            // [3B][d] per-position rows of repeated ranks
+};
+int launch_loss(const LossParams& p, hipStream_t st);
+
+// scal = {loss, node-feature loss, sum |h_q|^2, variance} from launch_loss's partials
+int launch_loss_monitor(const float* part, int nparts, const float* colpart, int d, int B, float* scal,
+                        hipStream_t st);
+
+// The on-the-fly step's virtual nodes (fly.hip): virtual node j (rank of
+// x0 + j in the top set) gets its real id's summed G row, both with K = 1;
+// combine_dz as launch_loss.
+int launch_fly_fix(float* G, int* Kc, int64_t S_max, int d, const unsigned long long* bits, const uint32_t* prefix,
+                   const int* n_x, const int64_t* xids, int64_t x0, int64_t unit, int64_t x_cap, const int* nS,
+                   float* dZ, bool combine_dz, hipStream_t st);
+
+// The step's loss arithmetic on outputs given per position (the micro-batched
+// step, pinsage_training._train_batch_micro): Z [3][B][d] (call-major), every
+// position its own row (no repeated ranks, so the float atomics of det_put
+// each add into a zero: exact).  G [3][3B][d]: position (c, b)'s cotangent at
+// G[c][c*B + b].  scal: {loss, 0, sum |h_q|^2, variance} -- the same kernels
+// and reduction order as pinsage_engine_loss, so the same bits for the same
+// rows.  scratch: triplet_loss_scratch_bytes(B, d).
+int64_t triplet_loss_scratch_bytes(int64_t B, int64_t d);
+int launch_triplet_loss(const float* Z, int B, int d, float margin, float* G, void* scratch, float* scal,
+                        hipStream_t st);
+
+// torch.optim.Adam on n floats; coef as AdamSlice::coef
+int launch_adam(float* p, const float* g, float* m, float* v, int64_t n, const float* coef,
+                double beta1, double beta2, float eps, hipStream_t st);
+
 }  // namespace ps

@@ -1862,9 +1862,6 @@ int launch_gather_rows(const float* h, int64_t ldh, int64_t n_h, int d, const in
   return kOk;
 }
 
-// autograd: the output rows' cotangents go into the loss's accumulators (G slab
-// 0, K slab 0); dZ = K * G is formed by the fused head backward (or here, for
-// the unfused head: scale = true)
 int launch_dz_from_dout(const float* dout, int d, const int32_t* pr, int64_t n, const int* nS,
                         int64_t S_max, float* G, int* Kc, float* dZ, bool scale, const int* rank_off,
                         const int32_t* pos_sorted, float* Gp, hipStream_t st) {
@@ -1905,7 +1902,7 @@ int launch_reduce_slabs_2d(const float* part, int S, int64_t stride, int M, int 
   PS_CHECK_LAUNCH();
   return kOk;
 }
-// one layer's tables: p.* as in LayerPrep, S_max / N_max the set capacities
+
 int launch_layer_preps(const LayerPrep* p, const int64_t* S_max, const int64_t* N_max, int n, int T, hipStream_t st) {
   PS_REQUIRE(n >= 1 && n <= kMaxPrepLayers, kErrArg, "layer_prep: 1..4 layers per launch");
   LayerPreps a;
@@ -1954,13 +1951,6 @@ int launch_agg(const float* q, int hid, const int32_t* loc, const float* wloc, i
   return kOk;
 }
 
-// CSR of the neighbour slots by q row.  cnt must be zero on entry (zeroed once
-// by pinsage_engine_init_workspace, then left zero by the scan).  The count
-// kernel also zeroes dpq's rows (the dq kernel's atomic targets).
-// CSR of the neighbour slots by q row, plus the dq chunk list.  cnt must be
-// zero on entry (zeroed once by pinsage_engine_init_workspace, then left zero
-// by the scan).
-// dynamic LDS above 64 KiB must be allowed per kernel (once, outside capture)
 int csr_prepare() {
   static int rc = [] {
     if (hipFuncSetAttribute((const void*)csr_count_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -1978,87 +1968,74 @@ int csr_prepare() {
   return rc;
 }
 
-int64_t dq_chunk_capacity(int64_t S_max, int T, int64_t N_max);
-int launch_csr_build(const int32_t* loc, const float* wloc, const int* nS, int64_t S_max, int T, const int* nN,
-                     int64_t N_max, int* cnt, int* bsum, int* off, int* cursor, int* cbase, int2* occ2,
-                     int2* chunks, int* nchunks, int2* split, int* nsplit, float* dpq, int hid, hipStream_t st,
-                     int2* occ2_tmp) {
-  const int lds = (int)std::min<int64_t>(N_max, kLdsRows) * 4;
+int launch_csr_build(const CsrBuildParams& p, hipStream_t st) {
+  const int lds = (int)std::min<int64_t>(p.N_max, kLdsRows) * 4;
   // more rows than one histogram: (range, slice) items over a CU-wide grid
-  const int gb = N_max > kLdsRows ? kCsrRangeGrid : std::max(1, std::min(128, ceil_div(S_max * T, 2048)));
-  // dq writes every row it owns (no atomics), so dpq needs no zeroing
-  (void)dpq;
+  const int gb = p.N_max > kLdsRows ? kCsrRangeGrid : std::max(1, std::min(128, ceil_div(p.S_max * p.T, 2048)));
+  // (dq writes every row it owns, no atomics, so dpq needs no zeroing here)
   // PINSAGE_CSR_RANGES: the range cap (0: the per-wave global-atomic path
   // beyond one histogram; A/B and tests)
   const int max_ranges = getenv("PINSAGE_CSR_RANGES") ? atoi(getenv("PINSAGE_CSR_RANGES")) : kMaxRanges;
-  hipLaunchKernelGGL(csr_count_kernel, dim3(gb), dim3(1024), lds, st, loc, nS, T, nN, cnt,
-                     (float*)nullptr, hid, nsplit, max_ranges);
+  hipLaunchKernelGGL(csr_count_kernel, dim3(gb), dim3(1024), lds, st, p.loc, p.nS, p.T, p.nN, p.cnt,
+                     (float*)nullptr, p.hid, p.nsplit, max_ranges);
   PS_CHECK_LAUNCH();
   // one block scans small sets; from ~4k rows on its threads' serial runs
   // (N / 1024 rows each) outlast the two-launch form (C4 layer 1, ~15k rows:
   // 26 us in one block)
-  if (N_max <= 4096) {
-    hipLaunchKernelGGL(scan_small_kernel, dim3(1), dim3(1024), 0, st, cnt, nN, off, cursor, cbase, chunks,
-                       nchunks, split, nsplit);
+  if (p.N_max <= 4096) {
+    hipLaunchKernelGGL(scan_small_kernel, dim3(1), dim3(1024), 0, st, p.cnt, p.nN, p.off, p.cursor, p.cbase, p.chunks,
+                       p.nchunks, p.split, p.nsplit);
     PS_CHECK_LAUNCH();
   } else {
-    const int nb = ceil_div(N_max + 1, kScanChunk);
-    int2* bs = reinterpret_cast<int2*>(bsum);
-    hipLaunchKernelGGL(scan_block_sums_kernel, dim3(nb), dim3(kScanB), 0, st, cnt, nN, bs);
+    const int nb = ceil_div(p.N_max + 1, kScanChunk);
+    int2* bs = reinterpret_cast<int2*>(p.bsum);
+    hipLaunchKernelGGL(scan_block_sums_kernel, dim3(nb), dim3(kScanB), 0, st, p.cnt, p.nN, bs);
     PS_CHECK_LAUNCH();
-    hipLaunchKernelGGL(scan_apply_kernel, dim3(nb), dim3(kScanB), 0, st, cnt, nN, bs, off, cursor,
-                       cbase, chunks, nchunks, split, nsplit);
+    hipLaunchKernelGGL(scan_apply_kernel, dim3(nb), dim3(kScanB), 0, st, p.cnt, p.nN, bs, p.off, p.cursor,
+                       p.cbase, p.chunks, p.nchunks, p.split, p.nsplit);
     PS_CHECK_LAUNCH();
   }
-  hipLaunchKernelGGL(csr_fill_kernel, dim3(gb), dim3(1024), lds, st, loc, wloc, nS, T, nN, cursor, off, cbase,
-                     occ2, max_ranges, split, nsplit, chunks);
+  hipLaunchKernelGGL(csr_fill_kernel, dim3(gb), dim3(1024), lds, st, p.loc, p.wloc, p.nS, p.T, p.nN, p.cursor, p.off,
+                     p.cbase, p.occ2, max_ranges, p.split, p.nsplit, p.chunks);
   PS_CHECK_LAUNCH();
   // canonical pair order (sorted by source row): bitwise-reproducible sums
-  if (occ2_tmp) {
-    const int64_t max_chunks = dq_chunk_capacity(S_max, T, N_max);
+  if (p.occ2_tmp) {
+    const int64_t max_chunks = dq_chunk_capacity(p.S_max, p.T, p.N_max);
     hipLaunchKernelGGL(csr_sort_chunks_kernel, dim3(grid_for(max_chunks * 64, 256, 2048)), dim3(256), 0, st,
-                       chunks, nchunks, off, occ2);
+                       p.chunks, p.nchunks, p.off, p.occ2);
     PS_CHECK_LAUNCH();
-    hipLaunchKernelGGL(csr_sort_rows_kernel, dim3(256), dim3(1024), kRankLds, st, split, nsplit, off, occ2,
-                       occ2_tmp);
+    hipLaunchKernelGGL(csr_sort_rows_kernel, dim3(256), dim3(1024), kRankLds, st, p.split, p.nsplit, p.off, p.occ2,
+                       p.occ2_tmp);
     PS_CHECK_LAUNCH();
   }
   return kOk;
 }
 
-// upper bound of the dq chunk list: one partial chunk per row plus full ones
 int64_t dq_chunk_capacity(int64_t S_max, int T, int64_t N_max) {
   return N_max + (S_max * T + kDqChunk - 1) / kDqChunk + 1;
 }
-// upper bound of the split-row list: a split row holds more than kDqChunk slots
 int64_t dq_split_capacity(int64_t S_max, int T) { return S_max * T / (kDqChunk + 1) + 1; }
-
-// levels of the split-row tree for rows of up to max_chunks chunks (fan-in 8)
 int dq_tree_levels(int64_t max_chunks) {
   int L = 1;
   for (int64_t n = 8; n < max_chunks; n *= 8) ++L;
   return L;
 }
 
-int launch_dq_chunks(const int2* chunks, const int* nchunks, int64_t max_chunks, const int2* split,
-                     const int* nsplit, int64_t max_split, const int* off, const int2* occ2,
-                     const float* dagg, int64_t ld_dagg, const float* q,
-                     int hid, float* dpq, float* part, hipStream_t st, const int32_t* q_src,
-                     int32_t* csrc, const int* cbase, int* tk, uint16_t* dpq3, int64_t ps3) {
-  PS_REQUIRE(hid % 4 == 0, kErrArg, "dq: hidden dim must be a multiple of 4");
+int launch_dq_chunks(const DqChunkParams& p, hipStream_t st) {
+  PS_REQUIRE(p.hid % 4 == 0, kErrArg, "dq: hidden dim must be a multiple of 4");
   // persistent waves (each prefetches its next chunk); 512 to 4096 blocks
   // measured alike at C2 (round 5), 1024 to 8192 at C2 and C4 (round 6), 2048
   // kept (PINSAGE_DQ_GRID: the cap, A/B)
   static const int grid_cap = getenv("PINSAGE_DQ_GRID") ? std::max(1, atoi(getenv("PINSAGE_DQ_GRID"))) : 2048;
-  const int grid = grid_for(max_chunks * 64, 256, grid_cap);
-  if (csrc) {  // chunk rows: masked partials in part, no combine
-    PS_REQUIRE(q_src, kErrArg, "dq: chunk rows need the rows' source indices");
-    if (hid >= 512)
-      hipLaunchKernelGGL((dq_chunk_kernel<2, true>), dim3(grid), dim3(256), 0, st, chunks, nchunks, occ2, dagg,
-                         ld_dagg, q, hid, dpq, part, q_src, csrc);
+  const int grid = grid_for(p.max_chunks * 64, 256, grid_cap);
+  if (p.csrc) {  // chunk rows: masked partials in part, no combine
+    PS_REQUIRE(p.q_src, kErrArg, "dq: chunk rows need the rows' source indices");
+    if (p.hid >= 512)
+      hipLaunchKernelGGL((dq_chunk_kernel<2, true>), dim3(grid), dim3(256), 0, st, p.chunks, p.nchunks, p.occ2, p.dagg,
+                         p.ld_dagg, p.q, p.hid, p.dpq, p.part, p.q_src, p.csrc);
     else
-      hipLaunchKernelGGL((dq_chunk_kernel<1, true>), dim3(grid), dim3(256), 0, st, chunks, nchunks, occ2, dagg,
-                         ld_dagg, q, hid, dpq, part, q_src, csrc);
+      hipLaunchKernelGGL((dq_chunk_kernel<1, true>), dim3(grid), dim3(256), 0, st, p.chunks, p.nchunks, p.occ2, p.dagg,
+                         p.ld_dagg, p.q, p.hid, p.dpq, p.part, p.q_src, p.csrc);
     PS_CHECK_LAUNCH();
     return kOk;
   }
@@ -2066,38 +2043,40 @@ int launch_dq_chunks(const int2* chunks, const int* nchunks, int64_t max_chunks,
   // each XCD gathers its eighth of d_agg from its own L2 -- was bitwise this
   // kernel and slower in the step: C2 0.398-0.406 -> 0.408-0.50 ms, C4
   // 0.426-0.431 -> 0.447-0.452, round 6; removed)
-  if (tk && cbase && hid <= 512 && dpq3) {  // the same, dpq written as bf16 planes
-    if (hid > 256)
-      hipLaunchKernelGGL((dq_chunk_kernel<2, false, true, true>), dim3(grid), dim3(256), 0, st, chunks, nchunks,
-                         occ2, dagg, ld_dagg, q, hid, dpq, part, nullptr, nullptr, off, cbase, tk, max_chunks, dpq3,
-                         ps3);
+  if (p.tk && p.cbase && p.hid <= 512 && p.dpq3) {  // the same, dpq written as bf16 planes
+    if (p.hid > 256)
+      hipLaunchKernelGGL((dq_chunk_kernel<2, false, true, true>), dim3(grid), dim3(256), 0, st, p.chunks, p.nchunks,
+                         p.occ2, p.dagg, p.ld_dagg, p.q, p.hid, p.dpq, p.part, nullptr, nullptr, p.off, p.cbase, p.tk,
+                         p.max_chunks, p.dpq3, p.ps3);
     else
-      hipLaunchKernelGGL((dq_chunk_kernel<1, false, true, true>), dim3(grid), dim3(256), 0, st, chunks, nchunks,
-                         occ2, dagg, ld_dagg, q, hid, dpq, part, nullptr, nullptr, off, cbase, tk, max_chunks, dpq3,
-                         ps3);
+      hipLaunchKernelGGL((dq_chunk_kernel<1, false, true, true>), dim3(grid), dim3(256), 0, st, p.chunks, p.nchunks,
+                         p.occ2, p.dagg, p.ld_dagg, p.q, p.hid, p.dpq, p.part, nullptr, nullptr, p.off, p.cbase, p.tk,
+                         p.max_chunks, p.dpq3, p.ps3);
     PS_CHECK_LAUNCH();
     return kOk;
   }
-  PS_REQUIRE(!dpq3, kErrArg, "dq: planes output needs the split-row tree and hid <= 512");
-  if (tk && cbase && hid <= 512) {  // split rows combined by their own chunks (no combine launch)
-    if (hid > 256)
-      hipLaunchKernelGGL((dq_chunk_kernel<2, false, true>), dim3(grid), dim3(256), 0, st, chunks, nchunks, occ2,
-                         dagg, ld_dagg, q, hid, dpq, part, nullptr, nullptr, off, cbase, tk, max_chunks);
+  PS_REQUIRE(!p.dpq3, kErrArg, "dq: planes output needs the split-row tree and hid <= 512");
+  if (p.tk && p.cbase && p.hid <= 512) {  // split rows combined by their own chunks (no combine launch)
+    if (p.hid > 256)
+      hipLaunchKernelGGL((dq_chunk_kernel<2, false, true>), dim3(grid), dim3(256), 0, st, p.chunks, p.nchunks, p.occ2,
+                         p.dagg, p.ld_dagg, p.q, p.hid, p.dpq, p.part, nullptr, nullptr, p.off, p.cbase, p.tk,
+                         p.max_chunks);
     else
-      hipLaunchKernelGGL((dq_chunk_kernel<1, false, true>), dim3(grid), dim3(256), 0, st, chunks, nchunks, occ2,
-                         dagg, ld_dagg, q, hid, dpq, part, nullptr, nullptr, off, cbase, tk, max_chunks);
+      hipLaunchKernelGGL((dq_chunk_kernel<1, false, true>), dim3(grid), dim3(256), 0, st, p.chunks, p.nchunks, p.occ2,
+                         p.dagg, p.ld_dagg, p.q, p.hid, p.dpq, p.part, nullptr, nullptr, p.off, p.cbase, p.tk,
+                         p.max_chunks);
     PS_CHECK_LAUNCH();
     return kOk;
   }
-  if (hid >= 512)
-    hipLaunchKernelGGL((dq_chunk_kernel<2>), dim3(grid), dim3(256), 0, st, chunks, nchunks, occ2, dagg, ld_dagg,
-                       q, hid, dpq, part);
+  if (p.hid >= 512)
+    hipLaunchKernelGGL((dq_chunk_kernel<2>), dim3(grid), dim3(256), 0, st, p.chunks, p.nchunks, p.occ2, p.dagg,
+                       p.ld_dagg, p.q, p.hid, p.dpq, p.part);
   else
-    hipLaunchKernelGGL((dq_chunk_kernel<1>), dim3(grid), dim3(256), 0, st, chunks, nchunks, occ2, dagg, ld_dagg,
-                       q, hid, dpq, part);
+    hipLaunchKernelGGL((dq_chunk_kernel<1>), dim3(grid), dim3(256), 0, st, p.chunks, p.nchunks, p.occ2, p.dagg,
+                       p.ld_dagg, p.q, p.hid, p.dpq, p.part);
   PS_CHECK_LAUNCH();
-  hipLaunchKernelGGL(dq_combine_kernel, dim3((int)std::max<int64_t>(1, std::min<int64_t>(max_split, 512))),
-                     dim3(1024), 0, st, split, nsplit, off, part, q, hid, dpq);
+  hipLaunchKernelGGL(dq_combine_kernel, dim3((int)std::max<int64_t>(1, std::min<int64_t>(p.max_split, 512))),
+                     dim3(1024), 0, st, p.split, p.nsplit, p.off, p.part, p.q, p.hid, p.dpq);
   PS_CHECK_LAUNCH();
   return kOk;
 }
@@ -2111,23 +2090,18 @@ int launch_norm_lrelu_bwd(const float* y, const float* nrm, const float* dy, int
   return kOk;
 }
 
-int launch_loss(const float* Z, int d, const int32_t* pos_rank, int B, float margin,
-                const float* feats, int64_t ld_f, int d_in, const int64_t* batch, float* G, int* Kc,
-                int64_t S_max, const int* nS, float* dZ, float* part, float* colpart, float* scal,
-                float* hinge, bool combine_dz, bool rep_sum, const int* rank_off, const int32_t* pos_sorted,
-                float* Gp, hipStream_t st) {
-  // G and Kc are zero on entry (init_workspace; then the head backward (or
-  // dz_combine) and the first backward kernel leave them zero)
-  PS_REQUIRE(d <= 256, kErrArg, "loss: out_dim must be <= 256");
-  PS_REQUIRE(d <= 1024 && 1024 % d == 0, kErrArg, "loss: needs an out_dim that divides 1024");
-  const int nblk = ceil_div(B, 4);
+int launch_loss(const LossParams& p, hipStream_t st) {
+  PS_REQUIRE(p.d <= 256, kErrArg, "loss: out_dim must be <= 256");
+  PS_REQUIRE(p.d <= 1024 && 1024 % p.d == 0, kErrArg, "loss: needs an out_dim that divides 1024");
+  const int nblk = ceil_div(p.B, 4);
   // (features past 64 FPL per lane are streamed after the row stores, one
   // waited round trip per 64 columns: C2's 1024 take 16 per lane instead)
-  const int fpl = d_in <= 128 ? 2 : d_in <= 256 ? 4 : d_in <= 512 ? 8 : 16;
-#define PS_LOSS(ZP, FP)                                                                           \
-  hipLaunchKernelGGL((loss_triple_kernel<ZP, FP>), dim3(nblk), dim3(256), 0, st, Z, d, pos_rank, B, \
-                     margin, feats, ld_f, d_in, batch, G, Kc, S_max, part, colpart, hinge, rank_off, Gp)
-  if (d <= 128) {
+  const int fpl = p.d_in <= 128 ? 2 : p.d_in <= 256 ? 4 : p.d_in <= 512 ? 8 : 16;
+#define PS_LOSS(ZP, FP)                                                                                       \
+  hipLaunchKernelGGL((loss_triple_kernel<ZP, FP>), dim3(nblk), dim3(256), 0, st, p.Z, p.d, p.pos_rank, p.B,   \
+                     p.margin, p.feats, p.ld_f, p.d_in, p.batch, p.G, p.Kc, p.S_max, p.part, p.colpart, p.hinge, \
+                     p.rank_off, p.Gp)
+  if (p.d <= 128) {
     if (fpl == 2) PS_LOSS(2, 2);
     else if (fpl == 4) PS_LOSS(2, 4);
     else if (fpl == 8) PS_LOSS(2, 8);
@@ -2140,19 +2114,17 @@ int launch_loss(const float* Z, int d, const int32_t* pos_rank, int B, float mar
   }
 #undef PS_LOSS
   PS_CHECK_LAUNCH();
-  // rep_sum false: the consumer (the fused head backward, head.hip) sums the
-  // repeated ranks' Gp rows itself, in the same order
-  PS_REQUIRE(rep_sum || !combine_dz, kErrArg, "loss: dz_combine reads G: the repeated ranks need rep_sum");
-  if (rep_sum && d <= 128)
-    hipLaunchKernelGGL((rep_sum_kernel<2, 3>), dim3(grid_for(S_max * 64, 256)), dim3(256), 0, st, rank_off,
-                       pos_sorted, nS, d, Gp, G, S_max);
-  else if (rep_sum)
-    hipLaunchKernelGGL((rep_sum_kernel<4, 3>), dim3(grid_for(S_max * 64, 256)), dim3(256), 0, st, rank_off,
-                       pos_sorted, nS, d, Gp, G, S_max);
+  PS_REQUIRE(p.rep_sum || !p.combine_dz, kErrArg, "loss: dz_combine reads G: the repeated ranks need rep_sum");
+  if (p.rep_sum && p.d <= 128)
+    hipLaunchKernelGGL((rep_sum_kernel<2, 3>), dim3(grid_for(p.S_max * 64, 256)), dim3(256), 0, st, p.rank_off,
+                       p.pos_sorted, p.nS, p.d, p.Gp, p.G, p.S_max);
+  else if (p.rep_sum)
+    hipLaunchKernelGGL((rep_sum_kernel<4, 3>), dim3(grid_for(p.S_max * 64, 256)), dim3(256), 0, st, p.rank_off,
+                       p.pos_sorted, p.nS, p.d, p.Gp, p.G, p.S_max);
   PS_CHECK_LAUNCH();
-  if (combine_dz) {
-    hipLaunchKernelGGL(dz_combine_kernel, dim3(grid_for(S_max * d, 1024, 256)), dim3(1024), 0, st, G,
-                       Kc, S_max, nS, d, dZ);
+  if (p.combine_dz) {
+    hipLaunchKernelGGL(dz_combine_kernel, dim3(grid_for(p.S_max * p.d, 1024, 256)), dim3(1024), 0, st, p.G,
+                       p.Kc, p.S_max, p.nS, p.d, p.dZ);
     PS_CHECK_LAUNCH();
   }
   return kOk;
@@ -2201,13 +2173,7 @@ int launch_fly_fix(float* G, int* Kc, int64_t S_max, int d, const unsigned long 
   return kOk;
 }
 
-// The step's loss arithmetic on outputs given per position (the micro-batched
-// step, pinsage_training._train_batch_micro): Z [3][B][d] (call-major), every
-// position its own row (no repeated ranks, so the float atomics of det_put
-// each add into a zero: exact).  G [3][3B][d]: position (c, b)'s cotangent at
-// G[c][c*B + b].  scal: {loss, 0, sum |h_q|^2, variance} -- the same kernels
-// and reduction order as pinsage_engine_loss, so the same bits for the same
-// rows.  scratch: triplet_loss_scratch_bytes(B, d).
+// launch_triplet_loss's positions: every position its own row, no position CSR
 __global__ void triplet_identity_kernel(int32_t* __restrict__ pos_rank, int B, int* __restrict__ rank_off) {
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < 3 * B; i += gridDim.x * blockDim.x)
     pos_rank[i] = (i % 3) * B + i / 3;  // position 3b + c -> row c*B + b
@@ -2219,13 +2185,6 @@ int64_t triplet_loss_scratch_bytes(int64_t B, int64_t d) {
   return align_up(3 * B * 4, 256) + align_up(9 * B * 4, 256) + align_up((nblk + 1) * 16, 256) +
          align_up((nblk + 1) * 2 * d * 4, 256) + 256;
 }
-
-int launch_loss(const float* Z, int d, const int32_t* pos_rank, int B, float margin, const float* feats, int64_t ld_f,
-                int d_in, const int64_t* batch, float* G, int* Kc, int64_t S_max, const int* nS, float* dZ, float* part,
-                float* colpart, float* scal, float* hinge, bool combine_dz, bool rep_sum, const int* rank_off,
-                const int32_t* pos_sorted, float* Gp, hipStream_t st);
-int launch_loss_monitor(const float* part, int nparts, const float* colpart, int d, int B, float* scal,
-                        hipStream_t st);
 
 int launch_triplet_loss(const float* Z, int B, int d, float margin, float* G, void* scratch, float* scal,
                         hipStream_t st) {
@@ -2246,8 +2205,19 @@ int launch_triplet_loss(const float* Z, int B, int d, float margin, float* G, vo
   hipLaunchKernelGGL(triplet_identity_kernel, dim3((unsigned)std::min<int64_t>((3LL * B + 255) / 256, 1024)),
                      dim3(256), 0, st, pos_rank, B, rank_off);
   PS_CHECK_LAUNCH();
-  PS_TRY(launch_loss(Z, d, pos_rank, B, margin, nullptr, 0, 0, nullptr, G, Kc, 3LL * B, nullptr, nullptr, part,
-                     colpart, scal, nullptr, false, false, rank_off, nullptr, nullptr, st));
+  LossParams l;
+  l.Z = Z;
+  l.d = d;
+  l.pos_rank = pos_rank;
+  l.B = B;
+  l.margin = margin;
+  l.G = G;
+  l.Kc = Kc;
+  l.S_max = 3LL * B;
+  l.part = part;
+  l.colpart = colpart;
+  l.rank_off = rank_off;
+  PS_TRY(launch_loss(l, st));
   return launch_loss_monitor(part, (int)nblk, colpart, d, B, scal, st);
 }
 

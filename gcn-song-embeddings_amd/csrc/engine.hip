@@ -26,60 +26,12 @@
 #include "aggw.h"
 #include "common.h"
 #include "conv.h"
+#include "frontier.h"
 #include "gemm.h"
+#include "head.h"
 #include "wgrad.h"
 
 namespace ps {
-
-// launchers from frontier.hip / conv.hip
-int64_t bitset_words(int64_t universe);
-int64_t bitset_blocks(int64_t universe);
-int launch_mark_i64(unsigned long long*, const int64_t*, int64_t, int64_t, int*, hipStream_t);
-int launch_mark_table(unsigned long long*, const int32_t*, const int*, int64_t, const int32_t*,
-                      int64_t, int, int64_t, hipStream_t);
-bool mark_finalize_fits(int64_t universe);
-int launch_mark_finalize(unsigned long long*, const int32_t*, const int*, int64_t, const int32_t*, int64_t, int,
-                         int64_t, int*, uint32_t*, int32_t*, int*, unsigned long long*, const unsigned long long*,
-                         uint32_t*, int32_t*, int*, hipStream_t);
-int launch_set_finalize(unsigned long long*, const unsigned long long*, const unsigned long long*,
-                        int64_t, uint32_t*, uint32_t*, int32_t*, int*, hipStream_t);
-int launch_top_set(unsigned long long*, int64_t, unsigned long long*, const int64_t*, int64_t,
-                   int64_t, uint32_t*, uint32_t*, int32_t*, int*, hipStream_t, int64_t x0 = 0,
-                   const int* x_n = nullptr);
-int launch_fly_fix(float*, int*, int64_t, int, const unsigned long long*, const uint32_t*, const int*, const int64_t*,
-                   int64_t, int64_t, int64_t, const int*, float*, bool, hipStream_t);
-
-int launch_agg(const float*, int, const int32_t*, const float*, int, const int*, int64_t, float*,
-               hipStream_t);
-int launch_csr_build(const int32_t*, const float*, const int*, int64_t, int, const int*, int64_t, int*, int*,
-                     int*, int*, int*, int2*, int2*, int*, int2*, int*, float*, int, hipStream_t, int2*);
-int64_t dq_chunk_capacity(int64_t, int, int64_t);
-int64_t dq_split_capacity(int64_t, int);
-int launch_dq_chunks(const int2*, const int*, int64_t, const int2*, const int*, int64_t, const int*,
-                     const int2*, const float*, int64_t, const float*, int, float*, float*, hipStream_t,
-                     const int32_t* q_src = nullptr, int32_t* csrc = nullptr, const int* cbase = nullptr,
-                     int* tk = nullptr, uint16_t* dpq3 = nullptr, int64_t ps3 = 0);
-int dq_tree_levels(int64_t max_chunks);
-int launch_norm_lrelu_bwd(const float*, const float*, const float*, int, const int*, int64_t,
-                          float*, float*, int, const int*, int*, int64_t, hipStream_t);
-int launch_loss(const float*, int, const int32_t*, int, float, const float*, int64_t, int,
-                const int64_t*, float*, int*, int64_t, const int*, float*, float*, float*, float*,
-                float*, bool, bool, const int*, const int32_t*, float*, hipStream_t);
-int launch_pos_csr(const int32_t*, int64_t, const int*, int*, int32_t*, hipStream_t);
-int launch_loss_monitor(const float*, int, const float*, int, int, float*, hipStream_t);
-int launch_adam(float*, const float*, float*, float*, int64_t, const float*, double, double, float,
-                hipStream_t);
-int csr_prepare();
-int launch_reduce_slabs_2d(const float*, int, int64_t, int, int, float*, int64_t, const float*,
-                           float*, const AdamSlice*, hipStream_t);
-int launch_gather_out(const float*, int, const int32_t*, int64_t, float*, hipStream_t);
-int launch_head_fwd(const float*, int, const int*, int64_t, const float*, const float*,
-                    const float*, float*, float*, hipStream_t);
-int launch_head_bwd(float*, int*, int64_t, float*, int, const int*, int64_t, const float*,
-                    const float*, const float*, const float*, const float*, float*, float*,
-                    const int*, const int32_t*, const float*, hipStream_t);
-int launch_dz_from_dout(const float*, int, const int32_t*, int64_t, const int*, int64_t, float*,
-                        int*, float*, bool, const int*, const int32_t*, float*, hipStream_t);
 
 struct EngineConfig {
   int64_t n_items;   // rows of the feature table (track universe)
@@ -626,8 +578,8 @@ static inline void with_sk(const Engine& E, void* ws, GemmParams& p) {
 // scatter targets).  engine_layers runs the projections, aggregations and the
 // head.  A trainer with two workspaces runs step i+1's frontier beside step
 // i's backward (pinsage_training._FusedStep).
-int engine_frontier(Engine& E, void* ws, const int64_t* ids_dev, int64_t n_pos, hipStream_t st,
-                    bool with_csr = true) {
+static int engine_frontier(Engine& E, void* ws, const int64_t* ids_dev, int64_t n_pos, hipStream_t st,
+                           bool with_csr = true) {
   const EngineConfig& c = E.cfg;
   PS_REQUIRE(E.feats && E.nb && E.wn && E.params, kErrArg, "engine: pointers not set");
   PS_REQUIRE(n_pos > 0 && n_pos <= c.max_pos, kErrArg, "engine: n_pos out of range");
@@ -660,10 +612,27 @@ int engine_frontier(Engine& E, void* ws, const int64_t* ids_dev, int64_t n_pos, 
     const int64_t ld_l = lb.nb_tab ? lb.ld_tab : E.ldT;
     if (mark_finalize_fits(n) && lb.S.cap > 0) {  // one launch: mark N_l, finalise N_l and S_{l-1}
       LayerBuf* lo = l > 0 ? &E.L[(size_t)l - 1] : nullptr;
-      PS_TRY(launch_mark_finalize(bits(lb.N), mem(lb.S), cnt(lb.S), lb.S.cap, nb_l, ld_l, T, n,
-                                  at<int>(ws, E.tickets) + l, pref(lb.N), mem(lb.N), cnt(lb.N),
-                                  lo ? bits(lo->S) : nullptr, bits(lb.S), lo ? pref(lo->S) : nullptr,
-                                  lo ? mem(lo->S) : nullptr, lo ? cnt(lo->S) : nullptr, st));
+      MarkFinalizeParams m;
+      m.bitsN = bits(lb.N);
+      m.membersS = mem(lb.S);
+      m.countS = cnt(lb.S);
+      m.max_count = lb.S.cap;
+      m.nb = nb_l;
+      m.ld = ld_l;
+      m.T = T;
+      m.universe = n;
+      m.fz.ticket = at<int>(ws, E.tickets) + l;
+      m.fz.prefN = pref(lb.N);
+      m.fz.memN = mem(lb.N);
+      m.fz.cntN = cnt(lb.N);
+      m.fz.bS = bits(lb.S);
+      if (lo) {
+        m.fz.dstS = bits(lo->S);
+        m.fz.prefS = pref(lo->S);
+        m.fz.memS = mem(lo->S);
+        m.fz.cntS = cnt(lo->S);
+      }
+      PS_TRY(launch_mark_finalize(m, st));
       continue;
     }
     PS_TRY(launch_mark_table(bits(lb.N), mem(lb.S), cnt(lb.S), lb.S.cap, nb_l, ld_l, T, n, st));
@@ -736,18 +705,33 @@ int engine_frontier(Engine& E, void* ws, const int64_t* ids_dev, int64_t n_pos, 
     LayerBuf& lb = E.L[(size_t)l];
     hipStream_t sl = (csr_fork == 1 && l == 0) ? s_fk : st;
     Timed tc(E, lname("fwd.csr", l), sl);
-    PS_TRY(launch_csr_build(at<int32_t>(ws, lb.loc), at<float>(ws, lb.wloc), cnt(lb.S), lb.S.cap, T, cnt(lb.N),
-                            lb.N.cap, at<int>(ws, lb.cnt), at<int>(ws, lb.bsum), at<int>(ws, lb.off),
-                            at<int>(ws, lb.cursor), at<int>(ws, lb.cbase), at<int2>(ws, lb.occ2),
-                            at<int2>(ws, lb.chunks), at<int>(ws, lb.nchunks), at<int2>(ws, lb.split),
-                            at<int>(ws, lb.nsplit), at<float>(ws, lb.dpq), (int)c.hid, sl,
-                            at<int2>(ws, lb.occ2b)));
+    CsrBuildParams cb;
+    cb.loc = at<int32_t>(ws, lb.loc);
+    cb.wloc = at<float>(ws, lb.wloc);
+    cb.nS = cnt(lb.S);
+    cb.S_max = lb.S.cap;
+    cb.T = T;
+    cb.nN = cnt(lb.N);
+    cb.N_max = lb.N.cap;
+    cb.hid = (int)c.hid;
+    cb.cnt = at<int>(ws, lb.cnt);
+    cb.bsum = at<int>(ws, lb.bsum);
+    cb.off = at<int>(ws, lb.off);
+    cb.cursor = at<int>(ws, lb.cursor);
+    cb.cbase = at<int>(ws, lb.cbase);
+    cb.occ2 = at<int2>(ws, lb.occ2);
+    cb.chunks = at<int2>(ws, lb.chunks);
+    cb.nchunks = at<int>(ws, lb.nchunks);
+    cb.split = at<int2>(ws, lb.split);
+    cb.nsplit = at<int>(ws, lb.nsplit);
+    cb.occ2_tmp = at<int2>(ws, lb.occ2b);
+    PS_TRY(launch_csr_build(cb, sl));
   }
   if (csr_fork) PS_TRY(dep(E, s_fk, st));  // join: nothing of this call stays on side[0]
   return kOk;
 }
 
-int engine_layers(Engine& E, void* ws, hipStream_t st) {
+static int engine_layers(Engine& E, void* ws, hipStream_t st) {
   const EngineConfig& c = E.cfg;
   PS_REQUIRE(E.feats && E.nb && E.wn && E.params, kErrArg, "engine: pointers not set");
   const int Lc = (int)c.n_layers, T = (int)c.T;
@@ -918,8 +902,8 @@ int engine_layers(Engine& E, void* ws, hipStream_t st) {
   return launch_gemm(g2, st);
 }
 
-int engine_forward(Engine& E, void* ws, const int64_t* ids_dev, int64_t n_pos, hipStream_t st,
-                   bool with_csr = true) {
+static int engine_forward(Engine& E, void* ws, const int64_t* ids_dev, int64_t n_pos, hipStream_t st,
+                          bool with_csr = true) {
   PS_TRY(engine_frontier(E, ws, ids_dev, n_pos, st, with_csr));
   return engine_layers(E, ws, st);
 }
@@ -1077,7 +1061,7 @@ static int weight_grad(Engine& E, void* ws, const WGrad& w, hipStream_t st, cons
 // gradient but layer 0's is complete when the call's stream reaches its end);
 // 1: layer 0 (after a stage-0 call on the same workspace).  A data-parallel
 // step all-reduces stage 0's gradients while stage 1 runs.
-int engine_backward(Engine& E, void* ws, hipStream_t st, const AdamStep* adam, int stage = -1) {
+static int engine_backward(Engine& E, void* ws, hipStream_t st, const AdamStep* adam, int stage = -1) {
   const EngineConfig& c = E.cfg;
   PS_REQUIRE(E.grads, kErrArg, "engine: grad buffer not set");
   PS_REQUIRE(!adam || (E.adam_m && E.adam_v), kErrArg, "engine: optimizer state not set");
@@ -1137,11 +1121,25 @@ int engine_backward(Engine& E, void* ws, hipStream_t st, const AdamStep* adam, i
   if (E.fused_head) {
     // the head backward forms dZ = sum_c K[c] G[c] from the loss's
     // accumulators as it loads its rows (and zeroes them), writing dZ for dG2
-    PS_TRY(launch_head_bwd(at<float>(ws, E.G), at<int>(ws, E.Kc), top.S.cap, at<float>(ws, E.dZ), o,
-                           cnt(top.S), top.S.cap, at<float>(ws, E.H1), E.params + E.pG1w,
-                           E.params + E.pG2w, at<float>(ws, top.y), at<float>(ws, top.nrm),
-                           at<float>(ws, E.dP1), at<float>(ws, top.dp), at<int>(ws, E.rank_off),
-                           at<int32_t>(ws, E.pos_sorted), E.reps_in_gp ? at<float>(ws, E.Gp) : nullptr, st));
+    HeadBwdParams hb;
+    hb.G = at<float>(ws, E.G);
+    hb.Kc = at<int>(ws, E.Kc);
+    hb.S_max = top.S.cap;
+    hb.dZ = at<float>(ws, E.dZ);
+    hb.o = o;
+    hb.nrows = cnt(top.S);
+    hb.max_rows = top.S.cap;
+    hb.H1 = at<float>(ws, E.H1);
+    hb.G1w = E.params + E.pG1w;
+    hb.G2w = E.params + E.pG2w;
+    hb.y = at<float>(ws, top.y);
+    hb.nrm = at<float>(ws, top.nrm);
+    hb.dP1 = at<float>(ws, E.dP1);
+    hb.dp = at<float>(ws, top.dp);
+    hb.rank_off = at<int>(ws, E.rank_off);
+    hb.pos_sorted = at<int32_t>(ws, E.pos_sorted);
+    hb.Gp = E.reps_in_gp ? at<float>(ws, E.Gp) : nullptr;
+    PS_TRY(launch_head_bwd(hb, st));
     PS_TRY(run_pend(E));  // the loss monitors (PINSAGE_DEFER_SIDE bit 1)
     PS_TRY(fork_late(s_wg, wgrad_g2));
   } else {
@@ -1288,14 +1286,30 @@ int engine_backward(Engine& E, void* ws, hipStream_t st, const AdamStep* adam, i
     // gradient on them and on the feature table's planes (wgrad_pl_kernel)
     const bool planes = l == 0 && E.fplanes && lb.dpq3 && E.dq_tree && !chunk_rows && hd <= 512 && E.wgrad_kw &&
                         wgrad_kw_supported(hd, d, -1, false) && (int64_t)(hd / 64) * (d / 64) <= E.kw_cnt_len;
-    PS_TRY(launch_dq_chunks(at<int2>(ws, lb.chunks), at<int>(ws, lb.nchunks), lb.max_chunks,
-                            at<int2>(ws, lb.split), at<int>(ws, lb.nsplit), lb.max_split,
-                            at<int>(ws, lb.off), at<int2>(ws, lb.occ2),
-                            at<float>(ws, lb.dagg), hd, at<float>(ws, lb.q), hd, at<float>(ws, lb.dpq),
-                            at<float>(ws, lb.dqpart), st, at<int32_t>(ws, lb.q_src),
-                            chunk_rows ? at<int32_t>(ws, lb.csrc) : nullptr,
-                            E.dq_tree ? at<int>(ws, lb.cbase) : nullptr, E.dq_tree ? at<int>(ws, lb.dqtk) : nullptr,
-                            planes ? at<uint16_t>(ws, lb.dpq3) : nullptr, lb.N.cap * hd));
+    DqChunkParams dq;
+    dq.chunks = at<int2>(ws, lb.chunks);
+    dq.nchunks = at<int>(ws, lb.nchunks);
+    dq.max_chunks = lb.max_chunks;
+    dq.split = at<int2>(ws, lb.split);
+    dq.nsplit = at<int>(ws, lb.nsplit);
+    dq.max_split = lb.max_split;
+    dq.off = at<int>(ws, lb.off);
+    dq.occ2 = at<int2>(ws, lb.occ2);
+    dq.dagg = at<float>(ws, lb.dagg);
+    dq.ld_dagg = hd;
+    dq.q = at<float>(ws, lb.q);
+    dq.hid = hd;
+    dq.dpq = at<float>(ws, lb.dpq);
+    dq.part = at<float>(ws, lb.dqpart);
+    dq.q_src = at<int32_t>(ws, lb.q_src);
+    if (chunk_rows) dq.csrc = at<int32_t>(ws, lb.csrc);
+    if (E.dq_tree) {
+      dq.cbase = at<int>(ws, lb.cbase);
+      dq.tk = at<int>(ws, lb.dqtk);
+    }
+    if (planes) dq.dpq3 = at<uint16_t>(ws, lb.dpq3);
+    dq.ps3 = lb.N.cap * hd;
+    PS_TRY(launch_dq_chunks(dq, st));
     PS_TRY(run_pend(E));
     WGrad q_wgrad;
     {
@@ -1379,7 +1393,7 @@ int engine_backward(Engine& E, void* ws, hipStream_t st, const AdamStep* adam, i
 // Zero the regions that kernels keep zero after use (loss G / Kc, CSR counts,
 // stream-K tickets):
 // once per workspace, before its first step.
-int engine_init_workspace(Engine& E, void* ws, hipStream_t st) {
+static int engine_init_workspace(Engine& E, void* ws, hipStream_t st) {
   const EngineConfig& c = E.cfg;
   // the side streams and events now, outside any capture (a stream or event
   // created while a graph is being captured would invalidate that capture)
@@ -1738,13 +1752,30 @@ int pinsage_engine_loss(pinsage_engine* e, void* ws, int64_t batch_size, float m
     // virtual nodes copy the summed rows)
     const bool fly = E->fly_nx != nullptr;
     E->reps_in_gp = E->fused_head && E->head_rep_sum && !fly;
-    PS_TRY(launch_loss(at<float>(ws, E->Z), (int)c.out, at<int32_t>(ws, E->pos_rank), (int)batch_size,
-                       margin, with_monitors ? E->feats : nullptr, E->ld_f, (int)c.d_in,
-                       at<int64_t>(ws, E->ids), at<float>(ws, E->G), at<int>(ws, E->Kc), top.S.cap,
-                       at<int>(ws, top.S.count), at<float>(ws, E->dZ), at<float>(ws, E->part),
-                       at<float>(ws, E->varpart), at<float>(ws, E->scal), at<float>(ws, E->hinge),
-                       !E->fused_head && !fly, !E->fused_head || !E->head_rep_sum || fly, at<int>(ws, E->rank_off),
-                       at<int32_t>(ws, E->pos_sorted), at<float>(ws, E->Gp), st));
+    LossParams lp;
+    lp.Z = at<float>(ws, E->Z);
+    lp.d = (int)c.out;
+    lp.pos_rank = at<int32_t>(ws, E->pos_rank);
+    lp.B = (int)batch_size;
+    lp.margin = margin;
+    lp.feats = with_monitors ? E->feats : nullptr;
+    lp.ld_f = E->ld_f;
+    lp.d_in = (int)c.d_in;
+    lp.batch = at<int64_t>(ws, E->ids);
+    lp.G = at<float>(ws, E->G);
+    lp.Kc = at<int>(ws, E->Kc);
+    lp.S_max = top.S.cap;
+    lp.nS = at<int>(ws, top.S.count);
+    lp.dZ = at<float>(ws, E->dZ);
+    lp.part = at<float>(ws, E->part);
+    lp.colpart = at<float>(ws, E->varpart);
+    lp.hinge = at<float>(ws, E->hinge);
+    lp.combine_dz = !E->fused_head && !fly;
+    lp.rep_sum = !E->fused_head || !E->head_rep_sum || fly;
+    lp.rank_off = at<int>(ws, E->rank_off);
+    lp.pos_sorted = at<int32_t>(ws, E->pos_sorted);
+    lp.Gp = at<float>(ws, E->Gp);
+    PS_TRY(launch_loss(lp, st));
     if (fly)
       PS_TRY(launch_fly_fix(at<float>(ws, E->G), at<int>(ws, E->Kc), top.S.cap, (int)c.out,
                             at<unsigned long long>(ws, top.S.bits), at<uint32_t>(ws, top.S.prefix), E->fly_nx,

@@ -21,20 +21,11 @@
 // neighbour id >= n sets err[1] (the reference's h[nb] raises there).
 #include <algorithm>
 
-#include "common.h"
+#include "fly.h"
+#include "frontier.h"
+#include "ppr_topk.h"
 
 namespace ps {
-
-int64_t bitset_words(int64_t universe);
-int launch_set_finalize(unsigned long long*, const unsigned long long*, const unsigned long long*, int64_t,
-                        uint32_t*, uint32_t*, int32_t*, int*, hipStream_t);
-int ppr_walk_lds_bytes(int n_hops, int* P_out);
-int launch_walk_runs_seg(const int64_t* indptr, const int32_t* indices, const int64_t* sources64,
-                         const int32_t* sources32, int64_t n_src_cap, const int* seg, int C, const uint64_t* seeds,
-                         int key_stride, int64_t id_unit, int n_hops, float alpha, uint32_t offset, uint2* runs,
-                         int* n_runs, int* err, hipStream_t st);
-int launch_heap_topk(const uint2*, const int*, int64_t, int, int, double*, int64_t*, float*, int32_t*, int,
-                     hipStream_t, const int* n_src_dev);
 
 constexpr int kFlyC = 3;  // calls per step (q, pos, neg)
 

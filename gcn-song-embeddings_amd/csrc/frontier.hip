@@ -4,13 +4,11 @@
 // track universe [0, n) is a bitmap: marking is one atomicOr per id, the
 // sorted unique list and every id's rank come from a per-word popcount prefix,
 // so no sort runs and ranks are O(1) lookups (bitmap + prefix stay in L2).
-#include "common.h"
+#include "frontier.h"
 
 #include <algorithm>
 
 namespace ps {
-
-int64_t bitset_words(int64_t universe);
 
 constexpr int kScanBlock = 256;
 constexpr int kWordsPerThread = 4;
@@ -103,23 +101,6 @@ __device__ __forceinline__ void finalize_block(unsigned long long* __restrict__ 
   }
   if (threadIdx.x == 1023) *count_out = (int)p;
 }
-
-// The finalisations a mark launch runs itself (its last block to finish, so
-// no separate single-block launch follows it): the marked set N (prefix,
-// members, count) and optionally S_lo = N | S_l.  ticket: a zeroed int (the
-// frontier's bitmap region, which the step's first kernel zeroes; the last
-// block also resets it).
-struct MarkFinalize {
-  int* ticket = nullptr;
-  uint32_t* prefN = nullptr;
-  int32_t* memN = nullptr;
-  int* cntN = nullptr;
-  unsigned long long* dstS = nullptr;  // null: N only
-  const unsigned long long* bS = nullptr;
-  uint32_t* prefS = nullptr;
-  int32_t* memS = nullptr;
-  int* cntS = nullptr;
-};
 
 // mark nb_table[members[f]][t] for f < *count, t < T (table row stride ld).
 // lds_words > 0: each block marks its contiguous slice into an LDS copy of the
@@ -421,26 +402,10 @@ int launch_mark_table(unsigned long long* bits, const int32_t* members, const in
   return launch_mark_table_fz(bits, members, count, max_count, nb, ld, T, universe, st, nullptr);
 }
 
-// whether launch_mark_table can finalise its set itself (single-block finalisation)
 bool mark_finalize_fits(int64_t universe) { return bitset_words(universe) <= kSmallWords; }
 
-// mark N from the table rows of S and finalise N (and S_lo = N | S_l when
-// dstS is set) in the same launch
-int launch_mark_finalize(unsigned long long* bitsN, const int32_t* membersS, const int* countS, int64_t max_count,
-                         const int32_t* nb, int64_t ld, int T, int64_t universe, int* ticket, uint32_t* prefN,
-                         int32_t* memN, int* cntN, unsigned long long* dstS, const unsigned long long* bS,
-                         uint32_t* prefS, int32_t* memS, int* cntS, hipStream_t st) {
-  MarkFinalize f;
-  f.ticket = ticket;
-  f.prefN = prefN;
-  f.memN = memN;
-  f.cntN = cntN;
-  f.dstS = dstS;
-  f.bS = bS;
-  f.prefS = prefS;
-  f.memS = memS;
-  f.cntS = cntS;
-  return launch_mark_table_fz(bitsN, membersS, countS, max_count, nb, ld, T, universe, st, &f);
+int launch_mark_finalize(const MarkFinalizeParams& p, hipStream_t st) {
+  return launch_mark_table_fz(p.bitsN, p.membersS, p.countS, p.max_count, p.nb, p.ld, p.T, p.universe, st, &p.fz);
 }
 
 int launch_mark_table_i64(unsigned long long* bits, const int64_t* ids, int64_t n,
@@ -481,13 +446,6 @@ int launch_set_rank_table(const int64_t* nodeset, int64_t n, const int32_t* nb, 
   return kOk;
 }
 
-// Finalise a set: dst = a | b, prefix, sorted members, device count.
-int launch_set_finalize(unsigned long long* dst, const unsigned long long* a,
-                        const unsigned long long* b, int64_t universe, uint32_t* block_sums,
-                        uint32_t* prefix, int32_t* members, int* count, hipStream_t st);
-
-// zero the bitmaps region [zero, zero + zero_words), mark ids into bits and
-// finalise that set (the top frontier of a step)
 int launch_top_set(unsigned long long* zero, int64_t zero_words, unsigned long long* bits,
                    const int64_t* ids, int64_t n, int64_t universe, uint32_t* block_sums,
                    uint32_t* prefix, int32_t* members, int* count, hipStream_t st, int64_t x0,

@@ -11,7 +11,7 @@
 // MFMA convention as in gemm.hip (v_mfma_f32_32x32x2_f32): in the r-th MFMA of
 // k-octet s, lane (l32, h) supplies k = 8s + 4h + r; accumulator element r of
 // lane (l32, h) is row (r & 3) + 8 (r >> 2) + 4h, column l32 of the 32 x 32 tile.
-#include "common.h"
+#include "head.h"
 
 #include <algorithm>
 
@@ -433,7 +433,7 @@ static int head_prepare() {
   return rc;
 }
 
-int head_supported(int64_t o) { return o > 0 && o <= kHeadDim && o % 4 == 0; }
+static int head_supported(int64_t o) { return o > 0 && o <= kHeadDim && o % 4 == 0; }
 
 int launch_head_fwd(const float* y, int o, const int* nrows, int64_t max_rows, const float* G1w,
                     const float* G1b, const float* G2w, float* H1, float* Z, hipStream_t st) {
@@ -446,20 +446,17 @@ int launch_head_fwd(const float* y, int o, const int* nrows, int64_t max_rows, c
   return kOk;
 }
 
-int launch_head_bwd(float* G, int* Kc, int64_t S_max, float* dZ, int o, const int* nrows,
-                    int64_t max_rows, const float* H1, const float* G1w, const float* G2w,
-                    const float* y, const float* nrm, float* dP1, float* dp, const int* rank_off,
-                    const int32_t* pos_sorted, const float* Gp, hipStream_t st) {
-  PS_REQUIRE(head_supported(o), kErrArg, "head: out_dim must be a multiple of 4, <= 128");
-  PS_REQUIRE(!Gp || (rank_off && pos_sorted), kErrArg, "head: repeated-rank rows need rank_off and pos_sorted");
+int launch_head_bwd(const HeadBwdParams& p, hipStream_t st) {
+  PS_REQUIRE(head_supported(p.o), kErrArg, "head: out_dim must be a multiple of 4, <= 128");
+  PS_REQUIRE(!p.Gp || (p.rank_off && p.pos_sorted), kErrArg, "head: repeated-rank rows need rank_off and pos_sorted");
   PS_TRY(head_prepare());
-  if (max_rows <= 0) return kOk;
+  if (p.max_rows <= 0) return kOk;
   // head_fetch_dz reads rank_off[0] whether or not the repeated ranks are
   // summed: without Gp any valid int works (the loss's Kc counters)
-  const int* ro = rank_off ? rank_off : Kc;
-  hipLaunchKernelGGL(head_bwd_kernel, dim3((unsigned)ceil_div(max_rows, kHeadRows)), dim3(256),
-                     kHeadBwdLds, st, G, Kc, S_max, dZ, o, nrows, H1, G1w, G2w, y, nrm, dP1, dp, ro,
-                     pos_sorted, Gp);
+  const int* ro = p.rank_off ? p.rank_off : p.Kc;
+  hipLaunchKernelGGL(head_bwd_kernel, dim3((unsigned)ceil_div(p.max_rows, kHeadRows)), dim3(256),
+                     kHeadBwdLds, st, p.G, p.Kc, p.S_max, p.dZ, p.o, p.nrows, p.H1, p.G1w, p.G2w, p.y, p.nrm, p.dP1,
+                     p.dp, ro, p.pos_sorted, p.Gp);
   PS_CHECK_LAUNCH();
   return kOk;
 }

@@ -19,8 +19,8 @@
 // select's four passes when the batch is sized to it.
 #include <algorithm>
 
-#include "common.h"
 #include "gemm.h"
+#include "knn.h"
 
 namespace ps {
 

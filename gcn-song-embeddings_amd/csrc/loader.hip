@@ -20,14 +20,9 @@
 #include <vector>
 
 #include "../../include/pinsage_hip.h"
-#include "common.h"
-#include "mt19937.h"
+#include "capi.h"
 
 namespace ps {
-
-int sample_batch_easy(MTState& g, const int64_t* positives, int64_t P, int64_t n_items,
-                      int64_t batch_size, int64_t* batch_out, int64_t* nodeset_out,
-                      int64_t* n_nodeset);
 
 namespace {
 

@@ -24,7 +24,7 @@
 // in LDS as 32-bit entries (count << 16 | ref, ref = id < k or k + run index),
 // at an odd stride so the 64 lanes' heaps sit in distinct banks.  The outputs
 // are written cooperatively (one source at a time, coalesced).
-#include "common.h"
+#include "ppr_topk.h"
 
 namespace ps {
 
@@ -316,7 +316,7 @@ __global__ __launch_bounds__(64) void heap_topk_kernel(
   }
 }
 
-int ppr_walk_lds_bytes(int n_hops, int* P_out) {
+static int ppr_walk_lds_bytes(int n_hops, int* P_out) {
   int P = 64;
   while (P < n_hops) P <<= 1;
   if (P_out) *P_out = P;

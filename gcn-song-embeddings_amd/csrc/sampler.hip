@@ -11,7 +11,7 @@
 // of every chunk of sources, one workgroup per chunk re-twists and tempers its
 // words into HBM.  "philox" is a counter-based Philox4x32-10 keyed by
 // (seed; hop, source position, offset) with a bit-exact CPU twin in oracle/.
-#include "common.h"
+#include "sampler.h"
 #include "mt19937.h"
 
 namespace ps {
@@ -470,7 +470,7 @@ int launch_walk(const int64_t* indptr, const int32_t* indices, const int64_t* so
   return kOk;
 }
 
-int visit_topk_lds_bytes(int64_t n_hops, int64_t k, int* P_out) {
+static int visit_topk_lds_bytes(int64_t n_hops, int64_t k, int* P_out) {
   int P = 64;
   while (P < n_hops) P <<= 1;
   if (P_out) *P_out = P;
