@@ -168,6 +168,9 @@ _SIGS = {
                                              vp]),
     "pinsage_knn_scratch_bytes": (i64, [i64, i64]),
     "pinsage_knn_cosine": (ctypes.c_int, [vp, i64, i64, i64, vp, i64, i64, f32, vp, i64, vp, vp, vp]),
+    "pinsage_rank_scratch_bytes": (i64, [i64, i64]),
+    "pinsage_rank_max_group": (i64, []),
+    "pinsage_rank_cosine": (ctypes.c_int, [vp, i64, i64, i64, vp, i64, vp, vp, i64, f32, vp, i64, vp, vp]),
     "pinsage_engine_create": (ctypes.c_int, [ctypes.POINTER(EngineConfig), ctypes.POINTER(vp)]),
     "pinsage_engine_destroy": (None, [vp]),
     "pinsage_engine_live_count": (i64, []),

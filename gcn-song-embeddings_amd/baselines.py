@@ -3,7 +3,11 @@ PinSage train step: personalised-PageRank
 neighbours (``PersPageRank``, baselines.py:106-151) on the walk + top-k
 kernels, and cosine k-nearest neighbours over an embedding table
 (``cosine_sim_ab`` / ``knn_from_emb``, baselines.py:69-103) with the
-``save_knn`` / ``load_knn`` cache format of eval.py:112-149.
+``save_knn`` / ``load_knn`` cache format of eval.py:112-149; and the accuracy
+metrics that consume them (``hit_rate`` / ``mrr`` / ``low_degree_accuracy``,
+eval.py:227-250 and :376-389), both over a kNN id matrix and over the ranks of
+the held-out positives, which ``rank_from_emb`` counts on the GPU without
+building any list.
 
 The reference's other baseline recommenders (node2vec, implicit ALS,
 networkx similarities, lib/gnns) are out of scope; their libraries are not
@@ -95,6 +99,174 @@ def knn_from_emb(emb, q, k, sim_func=None):
     return w[:, 1:], nb[:, 1:]
 
 
+RANK_MAX_GROUP = 4096  # kRankMaxGroup (csrc/knn.hip): targets one query row may own
+
+
+def _group_pairs(queries, targets):
+    """Group (query, target) pairs by query for pinsage_rank_cosine, on the
+    inputs' device (CPU tensors work too):
+    (rows int64 [nu], grp_ptr CPU int64 [nu + 1], targets_sorted int64 [np], order int64 [np]).
+    Row u is query rows[u] and owns targets_sorted[grp_ptr[u]:grp_ptr[u + 1]];
+    a query with more than RANK_MAX_GROUP pairs is repeated over several rows.
+    Sorted pair i is the caller's pair order[i] (a stable sort: pairs of one
+    query keep their order), so ``out[order] = sorted_result`` restores it."""
+    uq, inv, counts = torch.unique(queries, return_inverse=True, return_counts=True)
+    order = torch.sort(inv, stable=True).indices
+    cap = int(RANK_MAX_GROUP)
+    counts = counts.cpu()
+    pieces = (counts + cap - 1) // cap
+    sizes = torch.full((int(pieces.sum()),), cap, dtype=torch.int64)
+    if sizes.numel():
+        sizes[torch.cumsum(pieces, 0) - 1] = counts - (pieces - 1) * cap  # a query's last row: the rest
+    grp_ptr = torch.zeros(sizes.numel() + 1, dtype=torch.int64)
+    torch.cumsum(sizes, 0, out=grp_ptr[1:])
+    rows = torch.repeat_interleave(uq, pieces.to(uq.device))
+    return rows.contiguous(), grp_ptr, targets[order].contiguous(), order
+
+
+def rank_from_emb(emb, queries, targets, eps=1e-16):
+    """For parallel id tensors (the two columns of ``test_positives``): the
+    rank of row targets[i] among all rows of emb by cosine similarity to row
+    queries[i], int64 [len(queries)] on emb's device, in the order
+    ``knn_from_emb`` documents (similarity descending, index ascending): the
+    number of rows that come before the target.  ``_knn_cosine``'s column r for
+    that query holds the target exactly when rank == r, so ``knn_from_emb``'s
+    (which drops column 0) holds it at 1-based position rank.  HIP: dot
+    products of the distinct queries only and one counting pass per row; no
+    selection, no sort, no k-wide result."""
+    nat.require_gpu()
+    e = torch.as_tensor(emb)
+    out_dev = e.device
+    e = e.to(device="cuda", dtype=torch.float32).contiguous()
+    qs = torch.as_tensor(queries).reshape(-1).to(torch.int64)
+    ts = torch.as_tensor(targets).reshape(-1).to(torch.int64)
+    if qs.numel() != ts.numel():
+        raise ValueError(f"rank: {qs.numel()} queries for {ts.numel()} targets")
+    n, d = int(e.shape[0]), int(e.shape[1])
+    for name, v in (("query", qs), ("target", ts)):
+        if v.numel() and (int(v.min()) < 0 or int(v.max()) >= n):
+            raise IndexError(f"rank: {name} ids out of range for {n} rows")
+    npairs = int(qs.numel())
+    if npairs == 0:
+        return torch.empty(0, dtype=torch.int64, device=out_dev)
+    if d % 4:  # the MFMA GEMM loads 16-byte row chunks: zero columns change no dot product
+        e = torch.nn.functional.pad(e, (0, 4 - d % 4))
+        d = int(e.shape[1])
+    rows_q, grp_ptr, tsorted, order = _group_pairs(qs.to("cuda"), ts.to("cuda"))
+    nu = int(rows_q.numel())
+    out = torch.empty(npairs, dtype=torch.int64, device="cuda")
+    L = nat.lib()
+    rows = max(1, min(nu, (KNN_SCRATCH_BYTES - 8 * n) // max(1, 4 * n)))
+    nbytes = L.pinsage_rank_scratch_bytes(n, rows)
+    scratch = torch.empty(nbytes, dtype=torch.uint8, device="cuda")
+    nat.check(L.pinsage_rank_cosine(nat.ptr(e), n, d, d, nat.ptr(rows_q), nu, nat.ptr(grp_ptr),
+                                    nat.ptr(tsorted), npairs, float(eps), nat.ptr(scratch), nbytes,
+                                    nat.ptr(out), nat.stream_ptr()), "rank_cosine")
+    ranks = torch.empty_like(out)
+    ranks[order] = out
+    return ranks.to(out_dev)
+
+
+# ----------------------------------------------------------------------------- accuracy metrics
+# eval.py:227-250 and :376-389, vectorised.  The matrix forms take the id
+# matrix of knn_from_emb / load_knn ([n_nodes, list_len], column 0 of the top
+# list already dropped); the rank forms take rank_from_emb's ranks of the same
+# pairs: a positive is among the first K columns iff 1 <= rank <= min(K,
+# list_len), at 1-based position rank (rank 0 is the column knn_from_emb drops
+# as "the query itself": a miss, as in the reference).
+_METRIC_CHUNK = 1 << 16  # pairs whose list rows are compared at once
+
+
+def _pairs(test_positives):
+    return torch.as_tensor(test_positives).to(torch.int64).reshape(-1, 2)
+
+
+def _positions(knn_mat, test_positives, K):
+    """1-based position of each pair's positive in knn_mat[q, :K], 0 if absent."""
+    km = torch.as_tensor(knn_mat)
+    tp = _pairs(test_positives).to(km.device)
+    out = torch.zeros(tp.shape[0], dtype=torch.int64, device=km.device)
+    for i in range(0, tp.shape[0], _METRIC_CHUNK):
+        c = tp[i:i + _METRIC_CHUNK]
+        eq = km[c[:, 0], :K] == c[:, 1:2]
+        if eq.shape[1]:
+            out[i:i + _METRIC_CHUNK] = torch.where(eq.any(1), eq.to(torch.int8).argmax(1) + 1, 0)
+    return out
+
+
+def _positions_from_ranks(ranks, K, list_len):
+    r = torch.as_tensor(ranks).to(torch.int64).reshape(-1)
+    return torch.where((r >= 1) & (r <= min(int(K), int(list_len))), r, 0)
+
+
+def _hit_rate(pos):
+    return int((pos > 0).sum()) / int(pos.numel())
+
+
+def _mrr(pos, K, scaling):
+    # a miss counts as position K (eval.py:248); summed in float64
+    rank_pos = torch.where(pos > 0, pos, int(K)).to(torch.float64)
+    return float((1.0 / (rank_pos / scaling)).sum()) / int(pos.numel())
+
+
+def hit_rate(knn_mat, test_positives, K):
+    """eval.py:227-238: the share of pairs (q, pos) with pos in knn_mat[q, :K]."""
+    return _hit_rate(_positions(knn_mat, test_positives, K))
+
+
+def mrr(knn_mat, test_positives, K, scaling=1):
+    """eval.py:240-250: mean of scaling / (1-based position of pos in knn_mat[q, :K]),
+    a miss counting as position K."""
+    return _mrr(_positions(knn_mat, test_positives, K), K, scaling)
+
+
+def hit_rate_from_ranks(ranks, K, list_len=PRECOMP_K):
+    """``hit_rate`` of a list_len-wide knn_from_emb matrix, from rank_from_emb's ranks."""
+    return _hit_rate(_positions_from_ranks(ranks, K, list_len))
+
+
+def mrr_from_ranks(ranks, K, scaling=1, list_len=PRECOMP_K):
+    """``mrr`` of a list_len-wide knn_from_emb matrix, from rank_from_emb's ranks."""
+    return _mrr(_positions_from_ranks(ranks, K, list_len), K, scaling)
+
+
+def _low_degree_selection(g, test_positives, degree_thr, queries):
+    """eval.py:379-385: which pairs have a query among the nodes whose
+    in-degree is at most degree_thr (None: no such node)."""
+    deg = torch.as_tensor(g.in_degrees(queries))
+    sel = queries[deg <= degree_thr]
+    if len(sel) == 0:
+        return None
+    return torch.isin(_pairs(test_positives)[:, 0].cpu(), sel)
+
+
+def low_degree_accuracy(knn_mat, g, test_positives, K, degree_thr, acc_func, queries=None, track_ids=None):
+    """eval.py:376-389: ``acc_func(knn_mat, pairs, K)`` (hit_rate or mrr) over the
+    pairs whose query has in-degree <= degree_thr in g (a graph.CSRGraph, or
+    anything answering ``in_degrees``); 0 if no node is that low."""
+    if queries is None:
+        queries = torch.arange(0, torch.as_tensor(knn_mat).shape[0], dtype=torch.int64)
+    keep = _low_degree_selection(g, test_positives, degree_thr, queries)
+    if keep is None:
+        return 0
+    return acc_func(knn_mat, _pairs(test_positives)[keep.to(_pairs(test_positives).device)], K)
+
+
+def low_degree_accuracy_from_ranks(ranks, g, test_positives, K, degree_thr, acc_func, queries=None,
+                                   n_nodes=None):
+    """``low_degree_accuracy`` from rank_from_emb's ranks of test_positives:
+    ``acc_func(ranks_of_the_kept_pairs, K)`` with hit_rate_from_ranks or
+    mrr_from_ranks.  The candidate nodes are ``queries``, else all n_nodes
+    (default: g.number_of_nodes()), the rows of the matrix form's knn_mat."""
+    if queries is None:
+        queries = torch.arange(0, g.number_of_nodes() if n_nodes is None else int(n_nodes), dtype=torch.int64)
+    keep = _low_degree_selection(g, test_positives, degree_thr, queries)
+    if keep is None:
+        return 0
+    r = torch.as_tensor(ranks).reshape(-1)
+    return acc_func(r[keep.to(r.device)], K)
+
+
 class PersPageRank(PredictionModel):
     """Nearest graph neighbours via PPR aka random walks with restarts
     (baselines.py:106-151): 1000 hops, restart 0.85; the walk consumes torch's
@@ -162,4 +334,6 @@ def load_knn(model_name, ids, save_dir):
 
 
 __all__ = ["PRECOMP_K", "PredictionModel", "EmbeddingModel", "cosine_sim_ab", "knn_from_emb",
-           "PersPageRank", "EmbeddingTable", "save_knn", "load_knn"]
+           "PersPageRank", "EmbeddingTable", "save_knn", "load_knn", "RANK_MAX_GROUP", "rank_from_emb",
+           "hit_rate", "mrr", "hit_rate_from_ranks", "mrr_from_ranks", "low_degree_accuracy",
+           "low_degree_accuracy_from_ranks"]

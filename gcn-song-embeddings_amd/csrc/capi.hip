@@ -748,6 +748,19 @@ int pinsage_knn_cosine(const float* emb, int64_t n, int64_t d, int64_t ld, const
                            nullptr, (hipStream_t)stream);
 }
 
+int64_t pinsage_rank_scratch_bytes(int64_t n, int64_t batch_rows) {
+  return rank_scratch_bytes(n, batch_rows < 1 ? 1 : batch_rows);
+}
+
+int64_t pinsage_rank_max_group(void) { return rank_max_group(); }
+
+int pinsage_rank_cosine(const float* emb, int64_t n, int64_t d, int64_t ld, const int64_t* queries,
+                        int64_t nu, const int64_t* grp_ptr, const int64_t* targets, int64_t np, float eps,
+                        void* scratch, int64_t scratch_bytes, int64_t* out_rank, void* stream) {
+  return launch_rank_cosine(emb, n, d, ld, queries, nu, grp_ptr, targets, np, eps, scratch, scratch_bytes,
+                            out_rank, nullptr, (hipStream_t)stream);
+}
+
 int pinsage_weighted_agg(const float* q, int64_t hid, const int32_t* loc, const float* w,
                          int64_t n_rows, int64_t T, float* agg, void* stream) {
   return launch_agg(q, (int)hid, loc, w, (int)T, nullptr, n_rows, agg, (hipStream_t)stream);

@@ -14,4 +14,21 @@ int launch_knn_cosine(const float* emb, int64_t n, int64_t d, int64_t ld, const 
                       int64_t k, float eps, void* scratch, int64_t scratch_bytes, float* out_w, int64_t* out_n,
                       int* err, hipStream_t st);
 
+// scratch bytes for rank batches of qb query rows over n table rows
+int64_t rank_scratch_bytes(int64_t n, int64_t qb);
+// most targets one query row may own (kRankMaxGroup)
+int rank_max_group();
+
+// out_rank [np]: for query row u and each of its targets t = targets[i],
+// grp_ptr[u] <= i < grp_ptr[u + 1], the number of rows j that come before t in
+// launch_knn_cosine's order for queries[u] (same key function):
+//   #{ j : key(j) > key(t) or (key(j) == key(t) and j < t) }.
+// grp_ptr is a HOST array [nu + 1] from 0 to np (checked before any launch; a
+// group holds at most rank_max_group() targets, a query id may repeat across
+// rows); queries, targets and out_rank are device arrays.  An id outside
+// [0, n) sets *err (device, nullable) and is clamped.
+int launch_rank_cosine(const float* emb, int64_t n, int64_t d, int64_t ld, const int64_t* queries, int64_t nu,
+                       const int64_t* grp_ptr, const int64_t* targets, int64_t np, float eps, void* scratch,
+                       int64_t scratch_bytes, int64_t* out_rank, int* err, hipStream_t st);
+
 }  // namespace ps

@@ -17,6 +17,11 @@
 // k-th key keep the lowest column indices; the final order is (sim desc,
 // index asc).  The row of dot products stays in the Infinity Cache across the
 // select's four passes when the batch is sized to it.
+//
+// The ranks of given rows in that order (the positives of held-out pairs:
+// eval.py:227-250 hit_rate / mrr) are counted without any list by
+// rank_count_kernel at the end of this file, over the same dot products,
+// norms and key function.
 #include <algorithm>
 
 #include "gemm.h"
@@ -33,6 +38,11 @@ __device__ __forceinline__ uint32_t f2key(float x) {
 }
 __device__ __forceinline__ float key2f(uint32_t k) {
   return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
+}
+// The key every kernel here orders by: the image of dot / (|q| |e_j| + eps),
+// (|q| |e_j| + eps) rounded like torch's rank-1 mm then add: no contraction
+__device__ __forceinline__ uint32_t knn_key(float dot, float na, float nj, float eps) {
+  return f2key(dot / __fadd_rn(__fmul_rn(na, nj), eps));
 }
 
 __global__ void knn_row_norms_kernel(const float* __restrict__ e, int64_t n, int d, int64_t ld,
@@ -160,8 +170,7 @@ __global__ __launch_bounds__(kKnnBlock) void knn_select_kernel(
   const float* row = dots + b * n;
   const float na = qn[b];
   auto key_of = [&](float dot, float nj) __attribute__((always_inline)) {
-    // (|a| |b| + eps) rounded like torch's rank-1 mm then add: no contraction
-    return f2key(dot / __fadd_rn(__fmul_rn(na, nj), eps));
+    return knn_key(dot, na, nj, eps);
   };
   auto key_at = [&](int64_t j) __attribute__((always_inline)) { return key_of(row[j], norms[j]); };
   // rows of n % 4 == 0 floats start 16-byte aligned (the dot rows are n apart)
@@ -457,6 +466,264 @@ int launch_knn_cosine(const float* emb, int64_t n, int64_t d, int64_t ld, const 
     PS_TRY(launch_gemm(p, st));
     hipLaunchKernelGGL(knn_select_kernel, dim3((unsigned)m), dim3(kKnnBlock), 0, st, dots, n, norms,
                        qn, eps, (int)k, P, out_w + q0 * k, out_n + q0 * k);
+    PS_CHECK_LAUNCH();
+  }
+  return kOk;
+}
+
+// ---------------------------------------------------------------- ranks of given rows
+// The rank of target row t for query q: how many rows j come before t in the
+// order above (key descending, index ascending).  hit_rate and mrr (eval.py:
+// 227-250) are functions of that one integer per (q, pos) pair, so neither
+// needs a list.  One workgroup per query row streams the row's keys ONCE and
+// ranks all m targets of its group in that pass:
+//   m <= kRankFew: the targets' (key, index) words sit in registers, each is
+//     counted by ballot + popcount into wave-private counts, combined in LDS;
+//   otherwise: the group is sorted best-first in LDS (knn_bitonic), each j
+//     binary-searches the first target it comes before and adds 1 to that slot
+//     of an LDS histogram; the inclusive prefix over the slots is the ranks.
+// Every count is an integer add: the result does not depend on the order.
+constexpr int kRankMaxGroup = 4096;  // targets of one query row (LDS: keys, ids, histogram)
+constexpr int kRankFew = 8;          // up to here the targets are held in registers
+
+// (key, index) as one integer: j comes before t exactly when word(j) > word(t)
+__device__ __forceinline__ uint64_t rank_word(uint32_t key, int32_t j) {
+  return ((uint64_t)key << 32) | (uint32_t)(0x7fffffff - j);
+}
+
+// visit(key, j, valid) over the keys of one row, every thread the same number
+// of times (visit may use wave-wide ballots): 4 x 16-byte loads of dots and
+// norms per thread where n % 4 == 0, the scalar path otherwise and for the tail.
+template <class Visit>
+__device__ __forceinline__ void rank_stream(const float* __restrict__ row, const float* __restrict__ norms,
+                                            int64_t n, float na, float eps, Visit visit) {
+  const int tid = threadIdx.x;
+  const int64_t n16 = (n % 4) == 0 ? (n / 16) * 16 : 0;
+  for (int64_t base = 0; base < n16; base += (int64_t)kKnnBlock * 16) {
+    const int64_t j0 = base + (int64_t)tid * 16;
+    const bool ok = j0 < n16;
+    const int64_t jl = ok ? j0 : 0;
+    float4 dv[4], nv[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      dv[u] = *reinterpret_cast<const float4*>(row + jl + 4 * u);
+      nv[u] = *reinterpret_cast<const float4*>(norms + jl + 4 * u);
+    }
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      visit(knn_key(dv[u].x, na, nv[u].x, eps), j0 + 4 * u, ok);
+      visit(knn_key(dv[u].y, na, nv[u].y, eps), j0 + 4 * u + 1, ok);
+      visit(knn_key(dv[u].z, na, nv[u].z, eps), j0 + 4 * u + 2, ok);
+      visit(knn_key(dv[u].w, na, nv[u].w, eps), j0 + 4 * u + 3, ok);
+    }
+  }
+  for (int64_t j0 = n16; j0 < n; j0 += kKnnBlock) {
+    const int64_t j = j0 + tid;
+    const bool ok = j < n;
+    visit(ok ? knn_key(row[j], na, norms[j], eps) : 0u, j, ok);
+  }
+}
+
+// first i in [0, m) with pred(i), or m: pred is false ... false true ... true
+template <class Pred>
+__device__ __forceinline__ int rank_first(int m, Pred pred) {
+  int lo = 0, hi = m;
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if (pred(mid)) hi = mid; else lo = mid + 1;
+  }
+  return lo;
+}
+
+__global__ __launch_bounds__(kKnnBlock) void rank_count_kernel(
+    const float* __restrict__ dots, int64_t n, const float* __restrict__ norms,
+    const float* __restrict__ qn, float eps, const int64_t* __restrict__ grp_ptr,
+    const int64_t* __restrict__ targets, int64_t* __restrict__ out_rank, int* __restrict__ err) {
+  __shared__ uint32_t skey[kRankMaxGroup];
+  __shared__ int32_t sidx[kRankMaxGroup];
+  __shared__ int hist[kRankMaxGroup];
+  __shared__ int wsum[kKnnBlock / 64][kRankFew];
+
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const int64_t b = blockIdx.x;
+  const float* row = dots + b * n;
+  const float na = qn[b];
+  const int64_t g0 = grp_ptr[b];
+  const int m = (int)(grp_ptr[b + 1] - g0);  // <= kRankMaxGroup (the launcher refuses more)
+  if (m <= 0) return;                        // block-uniform
+  auto target = [&](int i) {
+    int64_t t = targets[g0 + i];
+    if (t < 0 || t >= n) {  // callers validate; clamp so that no access strays
+      if (err) atomicExch(err, 1);
+      t = 0;
+    }
+    return (int32_t)t;
+  };
+  for (int i = tid; i < m; i += kKnnBlock) {
+    const int32_t t = target(i);
+    skey[i] = knn_key(row[t], na, norms[t], eps);
+    sidx[i] = t;
+  }
+  __syncthreads();
+
+  if (m <= kRankFew) {
+    uint64_t tw[kRankFew];
+    int cnt[kRankFew];  // wave-uniform
+#pragma unroll
+    for (int i = 0; i < kRankFew; ++i) {
+      tw[i] = i < m ? rank_word(skey[i], sidx[i]) : ~0ull;  // no word is above ~0
+      cnt[i] = 0;
+    }
+    rank_stream(row, norms, n, na, eps, [&](uint32_t key, int64_t j, bool valid) __attribute__((always_inline)) {
+      const uint64_t w = rank_word(key, (int32_t)j);
+#pragma unroll
+      for (int i = 0; i < kRankFew; ++i) cnt[i] += __popcll(__ballot(valid && w > tw[i]));
+    });
+    if (lane == 0) {
+#pragma unroll
+      for (int i = 0; i < kRankFew; ++i) wsum[wv][i] = cnt[i];
+    }
+    __syncthreads();
+    if (tid < m) {
+      int r = 0;
+      for (int w = 0; w < kKnnBlock / 64; ++w) r += wsum[w][tid];
+      out_rank[g0 + tid] = r;
+    }
+    return;
+  }
+
+  // ---- sorted form: slots in the final order, one histogram add per j
+  int P = 64;
+  while (P < m) P <<= 1;
+  for (int i = m + tid; i < P; i += kKnnBlock) {
+    skey[i] = 0u;
+    sidx[i] = 0x7fffffff;
+  }
+  for (int i = tid; i < m; i += kKnnBlock) hist[i] = 0;
+  __syncthreads();
+  knn_bitonic(skey, sidx, P);
+  rank_stream(row, norms, n, na, eps, [&](uint32_t key, int64_t j, bool valid) __attribute__((always_inline)) {
+    // the first target j comes before; j then comes before every later one too
+    const int s = !valid ? m : rank_first(m, [&](int i) {
+      const uint32_t sk = skey[i];
+      return key > sk || (key == sk && (int32_t)j < sidx[i]);
+    });
+    // a wave whose rows mostly share one slot (all below, or all above, the
+    // group) adds to it once, not 64 times on one address
+    const unsigned long long act = __ballot(s < m);
+    if (act) {
+      const int s0 = __shfl(s, __ffsll((long long)act) - 1, 64);
+      const unsigned long long same = __ballot(s == s0);
+      if (s == s0) {
+        if ((same & ((1ull << lane) - 1ull)) == 0) atomicAdd(&hist[s0], __popcll(same));
+      } else if (s < m) {
+        atomicAdd(&hist[s], 1);
+      }
+    }
+  });
+  __syncthreads();
+  // inclusive prefix over the m slots, in place: thread tid owns slots 4 tid .. 4 tid + 3
+  {
+    int v[4], s = 0;
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+      const int i = 4 * tid + c;
+      v[c] = i < m ? hist[i] : 0;
+      s += v[c];
+    }
+    int inc = s;
+    for (int o = 1; o < 64; o <<= 1) {
+      const int y = __shfl_up(inc, o, 64);
+      if (lane >= o) inc += y;
+    }
+    if (lane == 63) wsum[wv][0] = inc;
+    __syncthreads();
+    int run = inc - s;
+    for (int w = 0; w < wv; ++w) run += wsum[w][0];
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+      const int i = 4 * tid + c;
+      run += v[c];
+      if (i < m) hist[i] = run;
+    }
+  }
+  __syncthreads();
+  // back to the caller's order: a target finds its own slot (a target listed
+  // twice holds two equal slots; either one carries the same prefix)
+  for (int i = tid; i < m; i += kKnnBlock) {
+    const int32_t t = target(i);
+    const uint32_t key = knn_key(row[t], na, norms[t], eps);
+    const int s = rank_first(m, [&](int c) {
+      const uint32_t sk = skey[c];
+      return !(sk > key || (sk == key && sidx[c] < t));
+    });
+    out_rank[g0 + i] = hist[s];
+  }
+}
+
+int64_t rank_scratch_bytes(int64_t n, int64_t qb) {
+  return knn_scratch_bytes(n, qb) + align_up((qb + 1) * 8, 256);
+}
+
+int rank_max_group() { return kRankMaxGroup; }
+
+int launch_rank_cosine(const float* emb, int64_t n, int64_t d, int64_t ld, const int64_t* queries,
+                       int64_t nu, const int64_t* grp_ptr, const int64_t* targets, int64_t np, float eps,
+                       void* scratch, int64_t scratch_bytes, int64_t* out_rank, int* err, hipStream_t st) {
+  PS_REQUIRE(n > 0 && d > 0 && ld >= d && nu >= 0 && np >= 0, kErrArg, "rank: bad sizes");
+  PS_REQUIRE(d % 4 == 0, kErrArg, "rank: d must be a multiple of 4");
+  PS_REQUIRE(ld % 4 == 0 && (reinterpret_cast<uintptr_t>(emb) & 15) == 0, kErrArg,
+             "rank: ld must be a multiple of 4 and emb 16-byte aligned");
+  PS_REQUIRE(n <= INT32_MAX && d <= INT32_MAX, kErrArg, "rank: table too large");
+  PS_REQUIRE(grp_ptr != nullptr && grp_ptr[0] == 0, kErrArg, "rank: grp_ptr must start at 0");
+  for (int64_t u = 0; u < nu; ++u) {
+    const int64_t m = grp_ptr[u + 1] - grp_ptr[u];
+    PS_REQUIRE(m >= 0, kErrArg, "rank: grp_ptr must not decrease");
+    PS_REQUIRE(m <= kRankMaxGroup, kErrArg, "rank: a group holds more than 4096 targets (repeat the query row)");
+  }
+  PS_REQUIRE(grp_ptr[nu] == np, kErrArg, "rank: grp_ptr must end at the number of pairs");
+  if (nu == 0) return kOk;
+  // batch of query rows that fits the scratch
+  // (a row costs at least n * 4 + 16 bytes: start one above that bound and step down)
+  int64_t qb = std::min<int64_t>(nu, 65535);
+  qb = std::min<int64_t>(qb, std::max<int64_t>(1, (scratch_bytes - align_up(n * 4, 256)) / (n * 4 + 16) + 1));
+  while (qb > 1 && rank_scratch_bytes(n, qb) > scratch_bytes) --qb;
+  PS_REQUIRE(rank_scratch_bytes(n, qb) <= scratch_bytes, kErrWorkspace, "rank: scratch too small");
+  char* s = (char*)scratch;
+  float* norms = (float*)s;
+  s += align_up(n * 4, 256);
+  int32_t* q32 = (int32_t*)s;
+  s += align_up(qb * 4, 256);
+  float* qn = (float*)s;
+  s += align_up(qb * 4, 256);
+  int64_t* gp = (int64_t*)s;
+  s += align_up((qb + 1) * 8, 256);
+  float* dots = (float*)s;
+
+  hipLaunchKernelGGL(knn_row_norms_kernel, dim3((unsigned)ceil_div(n * 64, 256)), dim3(256), 0, st,
+                     emb, n, (int)d, ld, norms);
+  PS_CHECK_LAUNCH();
+  for (int64_t q0 = 0; q0 < nu; q0 += qb) {
+    const int64_t m = std::min(qb, nu - q0);
+    // the batch's slice of grp_ptr (absolute offsets into targets / out_rank)
+    PS_CHECK_HIP(hipMemcpyAsync(gp, grp_ptr + q0, (size_t)(m + 1) * 8, hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(knn_ids_kernel, dim3((unsigned)ceil_div(m, 256)), dim3(256), 0, st,
+                       queries + q0, m, n, q32, qn, norms, err);
+    PS_CHECK_LAUNCH();
+    GemmParams p;
+    p.M = (int)m;
+    p.N = (int)n;
+    p.K = (int)d;
+    p.a = emb;
+    p.lda = ld;
+    p.a_idx = q32;
+    p.b = emb;
+    p.ldb = ld;
+    p.c = dots;
+    p.ldc = n;
+    PS_TRY(launch_gemm(p, st));
+    hipLaunchKernelGGL(rank_count_kernel, dim3((unsigned)m), dim3(kKnnBlock), 0, st, dots, n, norms, qn, eps,
+                       gp, targets, out_rank, err);
     PS_CHECK_LAUNCH();
   }
   return kOk;

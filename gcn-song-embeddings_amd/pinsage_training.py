@@ -1520,6 +1520,29 @@ class PinSage:
                     self.embeddings[ids, :] = self.model(self.features, ids).to(self.embeddings.device)
         return self.embeddings
 
+    def evaluate(self, test_positives, ks=(10, 100, 500), mrr_k=1000, bsize=None):
+        """Hit rates and MRR of the current model over held-out pairs
+        ``test_positives`` [n, 2] (query id, positive id), as eval.py:413-427
+        ``compute_results_table`` names them: {"hr (k=10)": .., .., "mrr": ..}.
+        Embeds every track (``self.embeddings`` is left as ``embed`` leaves it)
+        and ranks each positive on the GPU (baselines.rank_from_emb): no kNN
+        lists.  Cheap enough to call between train steps: it draws nothing from
+        torch's generator and restores the model's train / eval mode, so the
+        next step is the one that would have run without it.  Under
+        data-parallel training every rank may call it and gets the same numbers."""
+        import baselines
+        self._sync_state()
+        was_training = self.model.training
+        try:
+            emb = self.embed(bsize=bsize)
+        finally:
+            self.model.train(was_training)
+        tp = torch.as_tensor(test_positives).to(torch.int64).reshape(-1, 2)
+        ranks = baselines.rank_from_emb(emb, tp[:, 0], tp[:, 1])
+        res = {f"hr (k={int(k)})": baselines.hit_rate_from_ranks(ranks, int(k)) for k in ks}
+        res["mrr"] = baselines.mrr_from_ranks(ranks, int(mrr_k), 1)
+        return res
+
     def _sync_state(self):
         for f in (self._fused, getattr(self, "_fused_fly", None)):
             if f is not None:

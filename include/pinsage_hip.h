@@ -637,6 +637,38 @@ int pinsage_knn_cosine(const float* emb, int64_t n, int64_t d, int64_t ld, const
                        int64_t nq, int64_t k, float eps, void* scratch, int64_t scratch_bytes,
                        float* out_w, int64_t* out_n, void* stream);
 
+/* ------------------------------------------------------------------ ranks of given rows
+ * hit_rate / mrr (eval.py:227-250) over held-out pairs (q, pos) without kNN
+ * lists: both are functions of one integer per pair, the rank of pos among all
+ * n rows under pinsage_knn_cosine's order for q.  Query row u (queries[u], an
+ * id that may repeat across rows) owns targets[grp_ptr[u] .. grp_ptr[u + 1]);
+ * for each of them
+ *   out_rank[i] = #{ j in [0, n) : key(j) > key(t) or (key(j) == key(t) and j < t) },  t = targets[i]
+ * with key the order-preserving image of sim(q, j) as pinsage_knn_cosine
+ * computes it (the same device function).  So for any k, column r of
+ * pinsage_knn_cosine's row for q holds t exactly when out_rank == r < k; a
+ * target is not counted against itself, and a target listed twice gets the
+ * same rank twice.  Ranks are integer counts: the result is deterministic.
+ * queries int64 [nu], targets int64 [np], out_rank int64 [np]: device (ids in
+ * [0, n), validated by the caller); grp_ptr int64 [nu + 1]: HOST memory, checked
+ * during the call and copied to the device on the stream (pageable memory is
+ * staged before the call returns; keep page-locked memory until the stream has
+ * run the call), from 0 to np, never decreasing, no group above
+ * pinsage_rank_max_group() = 4096 targets (split a larger group by repeating
+ * the query row).  emb, n, d, ld, eps as for pinsage_knn_cosine.  A refused
+ * call (PINSAGE_ERR_ARG: those size and alignment conditions, grp_ptr not
+ * starting at 0 / decreasing / not ending at np, a group above the capacity;
+ * PINSAGE_ERR_WORKSPACE: scratch below pinsage_rank_scratch_bytes(n, 1))
+ * launches nothing and leaves out_rank untouched.
+ * scratch: device bytes >= pinsage_rank_scratch_bytes(n, rows) for some batch
+ * of rows >= 1 (one batch: norms, one gathered-row GEMM, one counting pass of
+ * n * 8 B per query row). */
+int64_t pinsage_rank_scratch_bytes(int64_t n, int64_t batch_rows);
+int64_t pinsage_rank_max_group(void);
+int pinsage_rank_cosine(const float* emb, int64_t n, int64_t d, int64_t ld, const int64_t* queries,
+                        int64_t nu, const int64_t* grp_ptr, const int64_t* targets, int64_t np, float eps,
+                        void* scratch, int64_t scratch_bytes, int64_t* out_rank, void* stream);
+
 /* ------------------------------------------------------------------ train-step engine
  * PinSageModel.forward / PinSage.train_batch (pinsage_model.py:246-265,
  * pinsage_training.py:181-214) with device-resident sizes.  Parameters live in
