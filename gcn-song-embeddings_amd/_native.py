@@ -171,6 +171,10 @@ _SIGS = {
     "pinsage_rank_scratch_bytes": (i64, [i64, i64]),
     "pinsage_rank_max_group": (i64, []),
     "pinsage_rank_cosine": (ctypes.c_int, [vp, i64, i64, i64, vp, i64, vp, vp, i64, f32, vp, i64, vp, vp]),
+    "pinsage_row_inv_norms": (ctypes.c_int, [vp, i64, i64, i64, vp, vp]),
+    "pinsage_list_intra_sim": (ctypes.c_int, [vp, i64, i64, i64, vp, vp, i64, i64, i64, vp, vp, vp]),
+    "pinsage_list_overlap_max_k": (i64, []),
+    "pinsage_list_pair_overlap": (ctypes.c_int, [vp, i64, i64, i64, i64, vp, i64, vp, vp, vp]),
     "pinsage_engine_create": (ctypes.c_int, [ctypes.POINTER(EngineConfig), ctypes.POINTER(vp)]),
     "pinsage_engine_destroy": (None, [vp]),
     "pinsage_engine_live_count": (i64, []),

@@ -7,7 +7,9 @@ kernels, and cosine k-nearest neighbours over an embedding table
 metrics that consume them (``hit_rate`` / ``mrr`` / ``low_degree_accuracy``,
 eval.py:227-250 and :376-389), both over a kNN id matrix and over the ranks of
 the held-out positives, which ``rank_from_emb`` counts on the GPU without
-building any list.
+building any list; and the beyond-accuracy metrics of eval.py:255-374 and
+:445-467 (intra- and inter-list diversity, coverage, average degree) over a
+kNN id matrix, the two diversities on the kernels of csrc/listmetrics.hip.
 
 The reference's other baseline recommenders (node2vec, implicit ALS,
 networkx similarities, lib/gnns) are out of scope; their libraries are not
@@ -267,6 +269,170 @@ def low_degree_accuracy_from_ranks(ranks, g, test_positives, K, degree_thr, acc_
     return acc_func(r[keep.to(r.device)], K)
 
 
+# ----------------------------------------------------------------------------- beyond-accuracy metrics
+# eval.py:271-374 and :445-467.  knn_mat is the id matrix of knn_from_emb /
+# load_knn ([n queries, list_len]), on any device and of any integer dtype;
+# test_positives is accepted where the reference accepts it (only coverage with
+# all_nodes=False reads it).  Results are Python floats, as in the reference.
+LIST_OVERLAP_MAX_K = 4096  # kOvMaxK (csrc/listmetrics.hip): columns one pair of lists may compare
+
+
+def _lists(knn_mat):
+    """The id matrix as a contiguous int64 [n, list_len] tensor on the GPU."""
+    nat.require_gpu()
+    km = torch.as_tensor(knn_mat)
+    if km.dim() != 2:
+        raise ValueError(f"knn_mat must be [n, list_len], got {tuple(km.shape)}")
+    return km.to(device="cuda", dtype=torch.int64).contiguous()
+
+
+def _list_width(km, K):
+    kc = min(int(K), int(km.shape[1]))  # K above the list length: the whole list (a slice, in the reference)
+    if kc < 1:
+        raise ValueError(f"K = {K} over lists of {int(km.shape[1])} columns leaves nothing to measure")
+    return kc
+
+
+def _intra_sims(km, kc, features):
+    """float32 [n] on the GPU: per query the mean of the kc x kc cosine matrix of
+    its first kc recommended feature rows (HIP: inverse row norms, then one
+    gather-and-accumulate wave per query)."""
+    f = torch.as_tensor(features).to(device="cuda", dtype=torch.float32).contiguous()
+    if f.dim() != 2:
+        raise ValueError(f"features must be [N, d], got {tuple(f.shape)}")
+    n, d = int(f.shape[0]), int(f.shape[1])
+    nq, ldk = int(km.shape[0]), int(km.shape[1])
+    inv = torch.empty(n, dtype=torch.float32, device="cuda")
+    out = torch.empty(nq, dtype=torch.float32, device="cuda")
+    err = torch.zeros(1, dtype=torch.int32, device="cuda")
+    L = nat.lib()
+    nat.check(L.pinsage_row_inv_norms(nat.ptr(f), n, d, d, nat.ptr(inv), nat.stream_ptr()), "row_inv_norms")
+    nat.check(L.pinsage_list_intra_sim(nat.ptr(f), n, d, d, nat.ptr(inv), nat.ptr(km), nq, ldk, kc, nat.ptr(out),
+                                       nat.ptr(err), nat.stream_ptr()), "list_intra_sim")
+    if int(err):
+        raise IndexError(f"intra_diversity: recommended ids out of range for {n} feature rows")
+    return out
+
+
+def intra_diversity(knn_mat, test_positives, K, features):
+    """eval.py:271-286: 1 - the mean over queries of the mean cosine similarity
+    among the feature rows of knn_mat[q, :K] (the K x K matrix with its diagonal;
+    a repeated id counts as often as it is listed).  A recommended row of zeros
+    makes the result NaN, as in the reference.  The per-query values are fp32
+    from the kernel, their mean is taken in float64."""
+    km = _lists(knn_mat)
+    sims = _intra_sims(km, _list_width(km, K), features)
+    return 1 - float(sims.to(torch.float64).mean())
+
+
+def _pair_overlaps(km, kc, N, pairs):
+    """int32 [n_pairs, 3] (CPU numpy): |set(A)|, |set(B)|, |set(A) & set(B)| of the
+    first kc columns of the two rows of each pair (HIP)."""
+    if kc > LIST_OVERLAP_MAX_K:
+        raise ValueError(f"inter_diversity: K = {kc} above the kernel's capacity of {LIST_OVERLAP_MAX_K} columns")
+    if not 1 <= int(N) < 2 ** 31:
+        raise ValueError(f"inter_diversity: N = {N} ids do not fit 32 bits")
+    nq, ldk = int(km.shape[0]), int(km.shape[1])
+    pr = torch.as_tensor(pairs).to(torch.int64).reshape(-1, 2)
+    if pr.numel() and (int(pr.min()) < 0 or int(pr.max()) >= nq):
+        raise IndexError(f"inter_diversity: pair rows out of range for {nq} lists")
+    pr = pr.to("cuda").contiguous()
+    npairs = int(pr.shape[0])
+    out = torch.empty((npairs, 3), dtype=torch.int32, device="cuda")
+    err = torch.zeros(1, dtype=torch.int32, device="cuda")
+    nat.check(nat.lib().pinsage_list_pair_overlap(nat.ptr(km), nq, ldk, kc, int(N), nat.ptr(pr), npairs,
+                                                  nat.ptr(out), nat.ptr(err), nat.stream_ptr()),
+              "list_pair_overlap")
+    if int(err):
+        raise IndexError(f"inter_diversity: recommended ids out of range for N = {N}")
+    return out.cpu().numpy()
+
+
+def inter_diversity(knn_mat, test_positives, K, N, n_pairs=10000, pairs=None):
+    """eval.py:288-312: the mean cosine distance between the one-hot images of
+    knn_mat[a, :K] and knn_mat[b, :K] over sampled pairs of queries, i.e.
+    1 - |A & B| / sqrt(|A| |B|) over the SETS of ids (a repeated id marks one
+    column).  With ``pairs`` None the pairs are the reference's one draw,
+    ``np.random.randint(0, n, (n_pairs, 2))`` from numpy's global generator;
+    with ``pairs`` ([m, 2] rows of knn_mat) nothing is drawn.  The set sizes are
+    integers from the kernel; distances and their mean are float64."""
+    import numpy as np
+    km = _lists(knn_mat)
+    kc = _list_width(km, K)
+    if pairs is None:
+        pairs = np.random.randint(0, int(km.shape[0]), (int(n_pairs), 2))
+    o = _pair_overlaps(km, kc, N, pairs).astype(np.float64)
+    return float(np.mean(1.0 - o[:, 2] / np.sqrt(o[:, 0] * o[:, 1])))
+
+
+def coverage(knn_mat, test_positives, K=500, all_nodes=True, queries=None):
+    """eval.py:342-355: distinct ids in columns 1 .. K of knn_mat (the reference
+    skips column 0 here) over the number of queries, knn_mat.shape[0] or the
+    distinct count of ``queries`` (the reference's ``if not queries`` raises on a
+    tensor; this is its evident intent).  all_nodes=False counts the distinct
+    ids of test_positives instead."""
+    km = _lists(knn_mat)
+    if all_nodes:
+        recs = km[:, 1:int(K) + 1].flatten()
+    else:
+        recs = torch.as_tensor(test_positives).to(device="cuda", dtype=torch.int64).flatten()
+    denom = int(km.shape[0]) if queries is None else int(torch.unique(torch.as_tensor(queries)).numel())
+    return int(torch.unique(recs).numel()) / denom
+
+
+def _rec_degrees(knn_mat, g, K):
+    """(in-degree of each distinct id in knn_mat[:, :K], how often the id is
+    listed, number of listed slots): int64 on the GPU.  g answers
+    ``in_degrees(ids)`` (graph.CSRGraph or a stand-in) once per distinct id."""
+    km = _lists(knn_mat)
+    recs = km[:, :int(K)].flatten()
+    ids, counts = torch.unique(recs, return_counts=True)
+    deg = torch.as_tensor(g.in_degrees(ids.cpu())).to(device="cuda", dtype=torch.int64)
+    return deg, counts, int(recs.numel())
+
+
+def average_degree(knn_mat, g, test_positives, K, queries=None):
+    """eval.py:357-364: the mean in-degree in g over all slots of knn_mat[:, :K]
+    (an exact integer sum, divided once)."""
+    deg, counts, slots = _rec_degrees(knn_mat, g, K)
+    return int((deg * counts).sum()) / slots if slots else float("nan")
+
+
+def degree_dist(knn_mat, g, test_positives, K, queries=None):
+    """eval.py:366-374: (sorted distinct in-degrees, how many slots of
+    knn_mat[:, :K] hold a node of that degree), int64 tensors on knn_mat's device."""
+    deg, counts, _ = _rec_degrees(knn_mat, g, K)
+    vals, inverse = torch.unique(deg, sorted=True, return_inverse=True)
+    hist = torch.zeros(vals.numel(), dtype=torch.int64, device=vals.device).index_add_(0, inverse, counts)
+    dev = torch.as_tensor(knn_mat).device
+    return vals.to(dev), hist.to(dev)
+
+
+def beyond_accuracy(knn_mat, g, features, k=100, n_pairs=10000, pairs=None):
+    """One model's row of compute_beyond_accuracy_table (eval.py:457-461) as a
+    dict with the reference's keys.  Draws from numpy's generator unless
+    ``pairs`` is given (see inter_diversity)."""
+    km = _lists(knn_mat)
+    n_feat = int(torch.as_tensor(features).shape[0])
+    return {
+        "intra diversity": intra_diversity(km, None, k, features),
+        "inter diversity": inter_diversity(km, None, k, n_feat, n_pairs=n_pairs, pairs=pairs),
+        "coverage": coverage(km, None, K=k),
+        "average degree": average_degree(km, g, None, k),
+    }
+
+
+def compute_beyond_accuracy_table(knn_dict, test_positives, g, features):
+    """eval.py:445-467: the beyond-accuracy metrics at k = 100 of every model of
+    knn_dict ({name: (weights, id matrix)}) as a pandas.DataFrame."""
+    import pandas as pd
+    results = {}
+    for model in knn_dict:
+        _, knn_mat = knn_dict[model]
+        results[model] = beyond_accuracy(knn_mat, g, features, k=100)
+    return pd.DataFrame.from_dict(results, orient="index")
+
+
 class PersPageRank(PredictionModel):
     """Nearest graph neighbours via PPR aka random walks with restarts
     (baselines.py:106-151): 1000 hops, restart 0.85; the walk consumes torch's
@@ -336,4 +502,5 @@ def load_knn(model_name, ids, save_dir):
 __all__ = ["PRECOMP_K", "PredictionModel", "EmbeddingModel", "cosine_sim_ab", "knn_from_emb",
            "PersPageRank", "EmbeddingTable", "save_knn", "load_knn", "RANK_MAX_GROUP", "rank_from_emb",
            "hit_rate", "mrr", "hit_rate_from_ranks", "mrr_from_ranks", "low_degree_accuracy",
-           "low_degree_accuracy_from_ranks"]
+           "low_degree_accuracy_from_ranks", "LIST_OVERLAP_MAX_K", "intra_diversity", "inter_diversity",
+           "coverage", "average_degree", "degree_dist", "beyond_accuracy", "compute_beyond_accuracy_table"]

@@ -15,6 +15,7 @@
 #include "frontier.h"
 #include "gemm.h"
 #include "knn.h"
+#include "listmetrics.h"
 #include "ppr_topk.h"
 #include "sampler.h"
 #include "wgrad.h"
@@ -759,6 +760,23 @@ int pinsage_rank_cosine(const float* emb, int64_t n, int64_t d, int64_t ld, cons
                         void* scratch, int64_t scratch_bytes, int64_t* out_rank, void* stream) {
   return launch_rank_cosine(emb, n, d, ld, queries, nu, grp_ptr, targets, np, eps, scratch, scratch_bytes,
                             out_rank, nullptr, (hipStream_t)stream);
+}
+
+int pinsage_row_inv_norms(const float* x, int64_t n, int64_t d, int64_t ld, float* inv, void* stream) {
+  return launch_row_inv_norms(x, n, d, ld, inv, (hipStream_t)stream);
+}
+
+int pinsage_list_intra_sim(const float* feat, int64_t n, int64_t d, int64_t ld, const float* inv,
+                           const int64_t* lists, int64_t nq, int64_t ldk, int64_t kc, float* out, int* err,
+                           void* stream) {
+  return launch_list_intra_sim(feat, n, d, ld, inv, lists, nq, ldk, kc, out, err, (hipStream_t)stream);
+}
+
+int64_t pinsage_list_overlap_max_k(void) { return list_overlap_max_k(); }
+
+int pinsage_list_pair_overlap(const int64_t* lists, int64_t nq, int64_t ldk, int64_t kc, int64_t n_ids,
+                              const int64_t* pairs, int64_t np, int32_t* out, int* err, void* stream) {
+  return launch_list_pair_overlap(lists, nq, ldk, kc, n_ids, pairs, np, out, err, (hipStream_t)stream);
 }
 
 int pinsage_weighted_agg(const float* q, int64_t hid, const int32_t* loc, const float* w,

@@ -27,6 +27,7 @@ import _native as nat
 import pinsage_model as psm
 
 BASE_RUN_DIR = "./runs"
+_BEYOND_QUERY_BATCH = 8192  # query rows per knn_from_emb call of evaluate_beyond_accuracy
 
 TEST_TRACK_INFO = None
 TEST_IDS = None
@@ -1542,6 +1543,33 @@ class PinSage:
         res = {f"hr (k={int(k)})": baselines.hit_rate_from_ranks(ranks, int(k)) for k in ks}
         res["mrr"] = baselines.mrr_from_ranks(ranks, int(mrr_k), 1)
         return res
+
+    def evaluate_beyond_accuracy(self, k=100, n_pairs=10000, pairs=None, bsize=None):
+        """The beyond-accuracy row of the current model, as eval.py:445-467
+        ``compute_beyond_accuracy_table`` names it: {"intra diversity": ..,
+        "inter diversity": .., "coverage": .., "average degree": ..} at list
+        length k.  Embeds every track (``self.embeddings`` is left as ``embed``
+        leaves it), builds ``knn_from_emb(emb, all ids, k + 1)`` in query batches
+        (k + 1 because coverage reads columns 1 .. k of a list whose first column
+        is already dropped), keeps the lists on the GPU and hands them to
+        baselines.beyond_accuracy with the trainer's own graph and features.
+        Like ``evaluate`` it restores the model's train / eval mode and draws
+        nothing from torch's generator.  It DOES draw from numpy's global
+        generator (the reference's one ``np.random.randint`` call for the pairs
+        of inter-list diversity) unless ``pairs`` ([m, 2] query rows) is given."""
+        import baselines
+        self._sync_state()
+        was_training = self.model.training
+        try:
+            emb = self.embed(bsize=bsize)
+        finally:
+            self.model.train(was_training)
+        emb = emb.to("cuda")
+        n = int(emb.shape[0])
+        lists = [baselines.knn_from_emb(emb, torch.arange(i, min(i + _BEYOND_QUERY_BATCH, n)), int(k) + 1)[1]
+                 for i in range(0, n, _BEYOND_QUERY_BATCH)]
+        return baselines.beyond_accuracy(torch.cat(lists, dim=0), self.g, self.features, k=int(k),
+                                         n_pairs=n_pairs, pairs=pairs)
 
     def _sync_state(self):
         for f in (self._fused, getattr(self, "_fused_fly", None)):

@@ -669,6 +669,50 @@ int pinsage_rank_cosine(const float* emb, int64_t n, int64_t d, int64_t ld, cons
                         int64_t nu, const int64_t* grp_ptr, const int64_t* targets, int64_t np, float eps,
                         void* scratch, int64_t scratch_bytes, int64_t* out_rank, void* stream);
 
+/* ------------------------------------------------------------------ beyond-accuracy list metrics
+ * The device work of compute_beyond_accuracy_table (eval.py:445-467).
+ *
+ * pinsage_row_inv_norms: inv[r] = 1 / sqrt(sum_c x[r][c]^2) over x f32 [n] rows
+ * of d floats, row stride ld >= d (the ld - d floats after a row are never
+ * read), IEEE square root and division (a squared norm that is a power of four
+ * has an exact inverse); a zero row gives +inf.  The lengths of eval.py:259
+ * (cosine_sim_mat), inverted once per table row instead of once per list slot.
+ *
+ * pinsage_list_intra_sim: what intra_diversity (eval.py:271-286) computes per
+ * query before its mean: for row i of lists (int64 [nq] rows of stride ldk, the
+ * first kc columns used, ids in [0, n))
+ *   out[i] = | sum_{c < kc} inv[id_c] * feat[id_c][:] |^2 / (float)(kc * kc),
+ * the mean of the kc x kc matrix of cosine_sim_mat (eval.py:255-264) over the
+ * listed rows, its diagonal and repeated ids included.  NaN rule: a listed row
+ * of zeros has inv = +inf, and inf * 0 makes that query's value NaN, as the
+ * reference's 0 / 0 does (it has no eps); other queries are unaffected.  The
+ * sum runs in slot order and the reduction order is fixed: two runs give the
+ * same bits.  feat / inv as for pinsage_row_inv_norms (inv [n] from it).
+ *
+ * pinsage_list_pair_overlap: what inter_diversity (eval.py:288-312) needs per
+ * sampled pair.  Set semantics: the reference marks one-hot columns, so a
+ * repeated id counts once; scipy's cosine distance between two such rows is
+ * 1 - |A & B| / sqrt(|A| |B|).  For pair p = (a, b) of pairs (int64 [np][2],
+ * rows of lists in [0, nq), a == b allowed), A = set(lists[a][:kc]) and B
+ * likewise:
+ *   out[3 p] = |A|,  out[3 p + 1] = |B|,  out[3 p + 2] = |A & B|   (int32).
+ * Ids lie in [0, n_ids), n_ids < 2^31; 1 <= kc <= pinsage_list_overlap_max_k()
+ * = 4096.
+ *
+ * All pointers are device memory.  err (nullable): a device int set to 1 when
+ * an id (or a pair's row) is out of range; the value is clamped so that no
+ * access strays, and the caller raises.  A refused call (PINSAGE_ERR_ARG: a
+ * null pointer other than err, kc < 1, kc > ldk, kc above the capacity,
+ * ld < d, a size out of range) returns before any launch and leaves the
+ * outputs untouched. */
+int pinsage_row_inv_norms(const float* x, int64_t n, int64_t d, int64_t ld, float* inv, void* stream);
+int pinsage_list_intra_sim(const float* feat, int64_t n, int64_t d, int64_t ld, const float* inv,
+                           const int64_t* lists, int64_t nq, int64_t ldk, int64_t kc, float* out, int* err,
+                           void* stream);
+int64_t pinsage_list_overlap_max_k(void);
+int pinsage_list_pair_overlap(const int64_t* lists, int64_t nq, int64_t ldk, int64_t kc, int64_t n_ids,
+                              const int64_t* pairs, int64_t np, int32_t* out, int* err, void* stream);
+
 /* ------------------------------------------------------------------ train-step engine
  * PinSageModel.forward / PinSage.train_batch (pinsage_model.py:246-265,
  * pinsage_training.py:181-214) with device-resident sizes.  Parameters live in
