@@ -82,6 +82,10 @@ _SIGS = {
     "pinsage_adam": (ctypes.c_int, [vp, vp, vp, vp, i64, vp, ctypes.c_double, ctypes.c_double, ctypes.c_float,
                                     vp]),
     "pinsage_norm_lrelu_backward_ex": (ctypes.c_int, [vp, vp, vp, vp, i64, i64, vp, vp, i64, vp, vp, i64, vp]),
+    "pinsage_walk_runs": (ctypes.c_int, [vp, vp, i64, vp, i64, i64, f32, vp, u64, u32, i64, vp, i64, vp, vp, vp, vp]),
+    "pinsage_runs_topk": (ctypes.c_int, [vp, vp, i64, i64, i64, vp, vp, vp, vp, vp, i64, vp]),
+    "pinsage_walk_runs_seg": (ctypes.c_int, [vp, vp, i64, vp, vp, i64, vp, i64, vp, i64, i64, i64, f32, u32, vp, vp,
+                                             vp, vp]),
     "pinsage_version": (ctypes.c_int, []),
     "pinsage_last_error": (ctypes.c_char_p, []),
     "pinsage_device_count": (ctypes.c_int, []),

@@ -173,6 +173,27 @@ int pinsage_sample_batch_easy(void* mt, const int64_t* positives, int64_t P, int
 }
 
 // ------------------------------------------------------------------ walks
+// One round's MT19937 words on the device: the generator's state at the start
+// of each of <= n_chunks_max chunks of sources (desc, staged to desc_dev), the
+// host generator advanced past the round's nr * per_src words, and the expand
+// launch that writes them to raw.  desc is reused by the caller's next round.
+static int mt_expand_round(MTState& g, std::vector<MTChunk>& desc, MTChunk* desc_dev, int64_t nr, int64_t per_src,
+                           uint32_t* raw, hipStream_t st) {
+  const int64_t n_chunks_max = (int64_t)desc.size();
+  const int64_t spc = (nr + n_chunks_max - 1) / n_chunks_max;  // sources per chunk
+  const int64_t n_chunks = (nr + spc - 1) / spc;
+  const int64_t wpc = spc * per_src;
+  for (int64_t c = 0; c < n_chunks; ++c) {
+    MTChunk& d = desc[(size_t)c];
+    std::memcpy(d.s, g.s, sizeof(d.s));
+    d.next = g.next;
+    d.avail = (uint32_t)g.avail();
+    g.skip(std::min(wpc, (nr - c * spc) * per_src));
+  }
+  PS_CHECK_HIP(hipMemcpyAsync(desc_dev, desc.data(), (size_t)n_chunks * sizeof(MTChunk), hipMemcpyHostToDevice, st));
+  return launch_mt_expand(desc_dev, n_chunks, wpc, nr * per_src, raw, st);
+}
+
 int64_t pinsage_walk_mt_workspace(int64_t n_src, int64_t n_hops) {
   const int64_t chunks = 1024;
   return align_up(chunks * (int64_t)sizeof(MTChunk), 256) + 256 +
@@ -199,20 +220,7 @@ int pinsage_walk_mt(const int64_t* indptr, const int32_t* indices, int64_t n_all
   PS_CHECK_HIP(hipMemsetAsync(err_dev, 0x7f, 4, st));
   for (int64_t r0 = 0; r0 < n_src; r0 += room) {
     const int64_t nr = std::min(room, n_src - r0);
-    const int64_t spc = (nr + kChunks - 1) / kChunks;  // sources per chunk
-    const int64_t n_chunks = (nr + spc - 1) / spc;
-    const int64_t wpc = spc * per_src;
-    for (int64_t c = 0; c < n_chunks; ++c) {
-      MTChunk& d = desc[(size_t)c];
-      std::memcpy(d.s, g.s, sizeof(d.s));
-      d.next = g.next;
-      d.avail = (uint32_t)g.avail();
-      const int64_t words = std::min(wpc, (nr - c * spc) * per_src);
-      g.skip(words);
-    }
-    PS_CHECK_HIP(hipMemcpyAsync(desc_dev, desc.data(), (size_t)n_chunks * sizeof(MTChunk),
-                                hipMemcpyHostToDevice, st));
-    PS_TRY(launch_mt_expand(desc_dev, n_chunks, wpc, nr * per_src, raw, st));
+    PS_TRY(mt_expand_round(g, desc, desc_dev, nr, per_src, raw, st));
     PS_TRY(launch_walk(indptr, indices, sources + r0, nr, n_hops, alpha, raw, 0, 0, 0,
                        trace + r0 * n_hops, err_dev, st));
     PS_CHECK_HIP(hipStreamSynchronize(st));  // desc host buffer is reused next round
@@ -300,20 +308,7 @@ int pinsage_ppr_topk(const int64_t* indptr, const int32_t* indices, int64_t n_al
   for (int64_t r0 = 0; r0 < n_src; r0 += R) {
     const int64_t nr = std::min(R, n_src - r0);
     if (use_mt) {
-      MTState& g = *reinterpret_cast<MTState*>(mt);
-      const int64_t spc = (nr + kPprChunks - 1) / kPprChunks;
-      const int64_t n_chunks = (nr + spc - 1) / spc;
-      const int64_t wpc = spc * per_src;
-      for (int64_t c = 0; c < n_chunks; ++c) {
-        MTChunk& d = desc[(size_t)c];
-        std::memcpy(d.s, g.s, sizeof(d.s));
-        d.next = g.next;
-        d.avail = (uint32_t)g.avail();
-        g.skip(std::min(wpc, (nr - c * spc) * per_src));
-      }
-      PS_CHECK_HIP(hipMemcpyAsync(desc_dev, desc.data(), (size_t)n_chunks * sizeof(MTChunk),
-                                  hipMemcpyHostToDevice, st));
-      PS_TRY(launch_mt_expand(desc_dev, n_chunks, wpc, nr * per_src, raw, st));
+      PS_TRY(mt_expand_round(*reinterpret_cast<MTState*>(mt), desc, desc_dev, nr, per_src, raw, st));
     }
     PS_TRY(launch_walk_runs(indptr, indices, sources + r0, nr, (int)n_hops, alpha,
                             use_mt ? raw : nullptr, seed, offset, src_base + r0, runs_dev, nr_dev,
@@ -1132,6 +1127,79 @@ int pinsage_norm_lrelu_backward_ex(const float* y, const float* norms, const flo
              kErrArg, "norm_lrelu_backward_ex: bad sizes");
   return launch_norm_lrelu_bwd(y, norms, dy, (int)out, nrows, n_max, dp, z, (int)z_n, z_rows, zi, zi_n,
                                (hipStream_t)stream);
+}
+
+// ------------------------------------------------------------------ the fused sampler's two halves (test entries)
+// the walk's zero-degree check, as pinsage_ppr_topk ends: synchronises
+static int walk_runs_err_check(const int32_t* err, hipStream_t st) {
+  int e = 0;
+  PS_CHECK_HIP(hipMemcpyAsync(&e, err, 4, hipMemcpyDeviceToHost, st));
+  PS_CHECK_HIP(hipStreamSynchronize(st));
+  if (e != 0x7f7f7f7f) {
+    set_error("walk: zero-degree node met (the reference's torch.randint(0) raises here)");
+    return kErrGraph;
+  }
+  return kOk;
+}
+
+int pinsage_walk_runs(const int64_t* indptr, const int32_t* indices, int64_t n_all, const int64_t* sources,
+                      int64_t n_src, int64_t n_hops, float alpha, void* mt, uint64_t seed, uint32_t offset,
+                      int64_t src_base, void* ws, int64_t ws_bytes, uint32_t* runs, int32_t* n_runs, int32_t* err,
+                      void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  PS_REQUIRE(n_src >= 0 && n_hops > 0 && n_all > 0, kErrArg, "walk_runs: bad sizes");
+  PS_REQUIRE(n_hops <= 8192, kErrArg, "walk_runs: n_hops too large for the LDS sort");
+  PS_REQUIRE(n_all < (int64_t)0xFFFFFFFF, kErrArg, "walk_runs: n_all must fit 32 bits");
+  PS_REQUIRE(indptr && indices && sources && runs && n_runs && err, kErrArg, "walk_runs: null pointer");
+  if (n_src == 0) return kOk;
+  uint32_t* raw = nullptr;
+  if (mt) {
+    const int64_t desc_bytes = align_up(kPprChunks * (int64_t)sizeof(MTChunk), 256);
+    PS_REQUIRE(ws && ws_bytes >= pinsage_walk_mt_workspace(n_src, n_hops), kErrWorkspace,
+               "walk_runs: workspace below pinsage_walk_mt_workspace(n_src, n_hops)");
+    raw = reinterpret_cast<uint32_t*>(static_cast<char*>(ws) + desc_bytes + 256);
+    std::vector<MTChunk> desc((size_t)kPprChunks);
+    PS_TRY(mt_expand_round(*reinterpret_cast<MTState*>(mt), desc, reinterpret_cast<MTChunk*>(ws), n_src,
+                           3 * n_hops, raw, st));
+    PS_CHECK_HIP(hipStreamSynchronize(st));  // desc is staged from this frame
+  }
+  PS_CHECK_HIP(hipMemsetAsync(err, 0x7f, 4, st));
+  PS_TRY(launch_walk_runs(indptr, indices, sources, n_src, (int)n_hops, alpha, raw, seed, offset, src_base,
+                          reinterpret_cast<uint2*>(runs), n_runs, err, st));
+  return walk_runs_err_check(err, st);
+}
+
+int pinsage_runs_topk(const uint32_t* runs, const int32_t* n_runs, int64_t n_src, int64_t n_hops, int64_t k,
+                      const int32_t* n_src_dev, double* w_out, int64_t* nb_out, float* wn_out, int32_t* nb32_out,
+                      int64_t t_norm, void* stream) {
+  PS_REQUIRE(n_src >= 0 && n_hops > 0 && runs && n_runs, kErrArg, "runs_topk: bad sizes");
+  PS_REQUIRE(k >= 1, kErrArg, "runs_topk: k out of range (torch: selected index k out of range)");
+  PS_REQUIRE(n_hops < 65536 && k + n_hops < 65536, kErrArg, "runs_topk: n_hops / k too large");
+  PS_REQUIRE(n_hops <= 8192, kErrArg, "runs_topk: n_hops too large for the LDS sort");
+  PS_REQUIRE(!w_out == !nb_out && !wn_out == !nb32_out, kErrArg, "runs_topk: an output pair is weights and ids");
+  PS_REQUIRE(!wn_out || (t_norm >= 1 && t_norm <= k), kErrArg, "runs_topk: t_norm must be in [1, k]");
+  return launch_heap_topk(reinterpret_cast<const uint2*>(runs), n_runs, n_src, (int)n_hops, (int)k, w_out, nb_out,
+                          wn_out, nb32_out, wn_out ? (int)t_norm : 0, (hipStream_t)stream, n_src_dev);
+}
+
+int pinsage_walk_runs_seg(const int64_t* indptr, const int32_t* indices, int64_t n_all, const int64_t* sources64,
+                          const int32_t* sources32, int64_t n_src_cap, const int32_t* seg, int64_t n_calls,
+                          const uint64_t* seeds, int64_t key_stride, int64_t id_unit, int64_t n_hops, float alpha,
+                          uint32_t offset, uint32_t* runs, int32_t* n_runs, int32_t* err, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  PS_REQUIRE(n_src_cap >= 0 && n_hops > 0 && n_all > 0, kErrArg, "walk_runs_seg: bad sizes");
+  PS_REQUIRE(n_hops <= 8192, kErrArg, "walk_runs_seg: n_hops too large for the LDS sort");
+  PS_REQUIRE(n_all < (int64_t)0xFFFFFFFF, kErrArg, "walk_runs_seg: n_all must fit 32 bits");
+  PS_REQUIRE(n_calls >= 1 && n_calls <= INT32_MAX && key_stride >= 1 && key_stride <= INT32_MAX && id_unit >= 0,
+             kErrArg, "walk_runs_seg: bad call table");
+  PS_REQUIRE(indptr && indices && !sources64 != !sources32 && seg && seeds && runs && n_runs && err, kErrArg,
+             "walk_runs_seg: null pointer (sources: exactly one of int64 / int32)");
+  if (n_src_cap == 0) return kOk;
+  PS_CHECK_HIP(hipMemsetAsync(err, 0x7f, 4, st));
+  PS_TRY(launch_walk_runs_seg(indptr, indices, sources64, sources32, n_src_cap, seg, (int)n_calls, seeds,
+                              (int)key_stride, id_unit, (int)n_hops, alpha, offset, reinterpret_cast<uint2*>(runs),
+                              n_runs, err, st));
+  return walk_runs_err_check(err, st);
 }
 
 }  // extern "C"

@@ -23,8 +23,10 @@ int launch_walk_runs_seg(const int64_t* indptr, const int32_t* indices, const in
 
 // Top k of every source's visit counts: out_w / out_nb [n_src][k] (f64 weights
 // and int64 ids, nullable) and out_wn / out_nb32 [n_src][T_norm] (the first
-// T_norm, weights normalised over the k; nullable).  n_src_dev (nullable): n_src
-// is a capacity and the count is on the device.
+// T_norm, weights divided by the sum of those T_norm; nullable).  A source
+// without runs gives zeros with ids 0..k-1 and 0 / 0 = NaN there, as
+// visit_topk_kernel does.  n_src_dev (nullable): n_src is a capacity and the
+// count is on the device.
 int launch_heap_topk(const uint2* runs, const int* n_runs, int64_t n_src, int n_hops, int k, double* out_w,
                      int64_t* out_nb, float* out_wn, int32_t* out_nb32, int T_norm, hipStream_t st,
                      const int* n_src_dev = nullptr);

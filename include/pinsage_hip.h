@@ -444,7 +444,8 @@ int pinsage_norm_lrelu_backward(const float* y, const float* norms, const float*
 /* ------------------------------------------------------------------ test entries
  * Nothing in the engine or the Python package's product path calls these: they
  * expose the engine's own launches, one at a time, to the tests
- * (tests/test_gpu_gemm_forms.py, tests/test_gpu_optimizer.py).
+ * (tests/test_gpu_gemm_forms.py, tests/test_gpu_optimizer.py,
+ * tests/test_gpu_sampler_edges.py).
  *
  * pinsage_gemm_params: one GEMM launch with every field of the library's
  * launch parameters (csrc/gemm.h GemmParams, which documents them) given by
@@ -556,6 +557,53 @@ int pinsage_adam(float* p, const float* g, float* m, float* v, int64_t n, const 
 int pinsage_norm_lrelu_backward_ex(const float* y, const float* norms, const float* dy, const int* nrows,
                                    int64_t n_max, int64_t out, float* dp, float* z, int64_t z_n,
                                    const int* z_rows, int* zi, int64_t zi_n, void* stream);
+/* The fused sampler's two halves (tests/test_gpu_sampler_edges.py): what
+ * pinsage_ppr_topk launches back to back, with the runs between them in caller
+ * memory.  A source's runs are the (node id, visit count) pairs of its walk in
+ * ascending id order, the source's own id dropped: runs uint32 [n_src][n_hops][2]
+ * (row stride n_hops pairs), n_runs int32 [n_src] pairs written per source;
+ * the pairs past n_runs[s] are not written.
+ *
+ * pinsage_walk_runs: the walk launch.  mt != null: MT19937 mode, the host state
+ * advanced by 3*n_hops*n_src draws, ws device bytes >= pinsage_walk_mt_workspace(
+ * n_src, n_hops) (one round; a smaller workspace is PINSAGE_ERR_WORKSPACE); mt ==
+ * null: Philox mode keyed as pinsage_walk_philox (ws unused).  err: one device
+ * int, set to 0x7f7f7f7f and then to the smallest index of a source whose walk
+ * met a zero-degree node (PINSAGE_ERR_GRAPH; that source gets n_runs = 0 and
+ * no runs, every other source its own).  n_hops <= 8192.  Synchronises.
+ *
+ * pinsage_runs_topk: the top-k launch over caller-supplied runs, outputs as
+ * pinsage_visit_topk (each pair null or both set).  n_src_dev (nullable): n_src
+ * is a capacity that sizes the grid and the live count is min(n_src,
+ * *n_src_dev) on the device; rows at and past it are not written.
+ * Preconditions the kernel does NOT check: per source ids strictly ascending,
+ * counts >= 1 summing to <= n_hops, 0 <= n_runs <= n_hops.  k >= 1, n_hops <=
+ * 8192, k + n_hops < 65536, t_norm in [1, k] with wn_out, and k small enough
+ * for one source's heap (k | 1 words) to fit the 64 KB of LDS: a refused call
+ * (PINSAGE_ERR_ARG) launches nothing.  There is no n_all: the row is as wide as
+ * the partial_sort regime needs (k * 64 <= n_all, every id < n_all).
+ * A source without runs (every hop came back to it): w_out is k zeros with ids
+ * 0 .. k-1 in libstdc++'s order, and wn_out is 0 / 0 = NaN in every column, as
+ * the reference's own division gives; pinsage_visit_topk writes the same bits.
+ * Does not synchronise.
+ *
+ * pinsage_walk_runs_seg: the on-the-fly sampler's walk launch (Philox): n_calls
+ * calls' sources sorted by call, seg int32 [n_calls + 1] (device) their segment
+ * starts, call c keyed by seeds[c * key_stride] (device) and numbering its
+ * sources from 0; a source is sources64[s] or sources32[s] (exactly one set)
+ * minus c * id_unit.  n_src_cap sizes the grid; slots at and past seg[n_calls]
+ * are not written.  err as pinsage_walk_runs.  Synchronises. */
+int pinsage_walk_runs(const int64_t* indptr, const int32_t* indices, int64_t n_all, const int64_t* sources,
+                      int64_t n_src, int64_t n_hops, float alpha, void* mt, uint64_t seed, uint32_t offset,
+                      int64_t src_base, void* ws, int64_t ws_bytes, uint32_t* runs, int32_t* n_runs, int32_t* err,
+                      void* stream);
+int pinsage_runs_topk(const uint32_t* runs, const int32_t* n_runs, int64_t n_src, int64_t n_hops, int64_t k,
+                      const int32_t* n_src_dev, double* w_out, int64_t* nb_out, float* wn_out, int32_t* nb32_out,
+                      int64_t t_norm, void* stream);
+int pinsage_walk_runs_seg(const int64_t* indptr, const int32_t* indices, int64_t n_all, const int64_t* sources64,
+                          const int32_t* sources32, int64_t n_src_cap, const int32_t* seg, int64_t n_calls,
+                          const uint64_t* seeds, int64_t key_stride, int64_t id_unit, int64_t n_hops, float alpha,
+                          uint32_t offset, uint32_t* runs, int32_t* n_runs, int32_t* err, void* stream);
 
 /* ------------------------------------------------------------------ step hand-off
  * (PinSage.train_batch, pinsage_training.py:181-214, as ONE graph launch per step)

@@ -1062,3 +1062,266 @@ def test_norm_lrelu_bwd_reference_is_autograd():
     # (0.01f against 0.01: 2.2e-8 relative in the slope's rows)
     assert np.abs(want - x.grad.numpy()).max() <= 1e-7 * np.abs(want).max()
     assert (bound > 0).all()
+
+
+# ----------------------------------------------------------------------------- fused sampler edges (sampler_util)
+def test_sampler_references_against_plain_loops():
+    """runs_from_trace, dense_from_runs and norm_pair (tests/sampler_util.py)
+    against loops over Python ints and floats."""
+    import sampler_util as su
+    rng = np.random.default_rng(0)
+    for n_hops, n_all, src in ((1, 5, 0), (24, 40, 7), (200, 30, 29), (64, 3, 1)):
+        trace = rng.integers(0, n_all, n_hops)
+        trace[rng.integers(0, n_hops)] = src
+        counts = {}
+        for v in trace.tolist():
+            if v != src:
+                counts[v] = counts.get(v, 0) + 1
+        want = [[i, counts[i]] for i in sorted(counts)]
+        got = su.runs_from_trace(trace, src)
+        assert got.dtype == np.int64 and got.shape == (len(want), 2) and got.tolist() == want
+        su.check_row_preconditions(got, n_hops, n_all)
+        dense = su.dense_from_runs(got, n_all, n_hops)
+        assert dense.dtype == np.float64 and dense.shape == (n_all,)
+        for j in range(n_all):
+            assert dense[j] == (counts.get(j, 0) / n_hops if j != src else 0.0)
+    assert su.runs_from_trace([4, 4, 4], 4).shape == (0, 2)          # every hop came back: no runs
+    w = np.array([[0.5, 0.25, 0.125, 0.0], [0.0, 0.0, 0.0, 0.0], [1 / 3, 1 / 3, 1 / 7, 1 / 24]])
+    nb = np.array([[9, 8, 70000, 1], [0, 1, 2, 3], [5, 6, 7, 8]])
+    for t in (1, 2, 4):
+        wn, nb32 = su.norm_pair(w, nb, t)
+        assert wn.dtype == np.float32 and nb32.dtype == np.int32 and wn.shape == (3, t)
+        for i in range(3):
+            s = 0.0
+            for j in range(t):
+                s += float(w[i, j])
+            for j in range(t):
+                if s == 0.0:
+                    assert np.isnan(wn[i, j])
+                else:
+                    assert wn[i, j] == np.float32(float(w[i, j]) / s)
+                assert nb32[i, j] == nb[i, j]
+
+
+_SAMPLER_SHAPES = [(24, 10), (24, 1), (24, 2), (24, 3), (24, 16), (200, 1), (200, 2), (200, 3), (200, 10), (200, 16)]
+
+
+def test_sampler_hand_built_rows_meet_the_kernel_preconditions():
+    """Every hand-built row of the top-k cases holds what heap_topk_kernel
+    assumes (ids strictly ascending, counts >= 1, nr <= n_hops, counts summing
+    to <= n_hops), the catalogue contains the shapes the issue names, the
+    precondition check itself rejects a bad row, and the G table is what the
+    launcher's rule gives."""
+    import sampler_util as su
+    for n_hops, k in _SAMPLER_SHAPES + [(24, 1000), (24, 8191), (24, 16383)]:
+        cat = su.topk_catalogue(n_hops, k, n_random=160 if k <= 16 else 0)
+        n_all = su.topk_n_all(k, n_hops)
+        assert k * 64 <= n_all
+        names = [nm for nm, _ in cat]
+        assert len(set(names)) == len(names)
+        for nm, r in cat:
+            assert r.dtype == np.int64 and r.ndim == 2 and r.shape[1] == 2, nm
+            su.check_row_preconditions(r, n_hops, n_all)
+        rows = dict(cat)
+        nrs = {len(r) for r in rows.values()}
+        assert {0, 1, 7, 8, 9, 15, 16, 17, n_hops} <= nrs, (n_hops, k)
+        n_below = lambda r: int((r[:, 0] < k).sum())
+        assert any(len(r) and n_below(r) == len(r) for r in rows.values())       # all runs below k
+        assert any(len(r) and n_below(r) == 0 for r in rows.values())            # all at or above k
+        # pure ties: more than k of them where a walk can give as many
+        assert any(len(r) > min(k, n_hops - 1) and len(set(r[:, 1])) == 1 for r in rows.values())
+        assert any(len(r) > 2 and (np.diff(r[:, 1]) > 0).all() for r in rows.values())
+        assert any(len(r) > 2 and (np.diff(r[:, 1]) < 0).all() for r in rows.values())
+        assert any(len(r) > 1 and r[:, 1].max() == n_hops - (len(r) - 1) for r in rows.values())
+        if k > 1:
+            assert any(0 < len(r) < k for r in rows.values())                     # fewer non-zero entries than k
+        if k >= 10:  # the first sparse run at index 0 / 7 / 8 / 9, tails on both sides of the prefetch width
+            for p in (0, 7, 8, 9):
+                tails = {len(r) - p for nm, r in cat if nm.startswith(f"first-sparse{p}-") and n_below(r) == p}
+                assert {1, 7, 8, 9} <= tails, (k, p, tails)
+        # a multiple of 8 sparse runs and one more / one fewer: nr - first sparse index
+        tail = {len(r) - n_below(r) for r in rows.values()}
+        assert {0, 1, 7, 8, 9, 15, 16, 17} <= tail
+    for bad in ([[3, 1], [3, 1]], [[5, 1], [4, 1]], [[1, 0]], [[1, 20], [2, 5]], [[i, 1] for i in range(25)]):
+        with pytest.raises(AssertionError):
+            su.check_row_preconditions(np.array(bad), 24)
+    for n_src, G in su.G_TABLE.items():
+        assert su.heap_G(n_src, 10) == G
+    for (k, n_src), G in su.G_LDS_TABLE.items():
+        assert su.heap_G(n_src, k) == G
+
+
+def _tie_heavy_rows(n, k, rng, rows=6):
+    """sparse float64 rows of few distinct values (count / 24), so that the k-th
+    place falls inside a tie and the tail is zeros"""
+    m = np.zeros((rows, n), np.float64)
+    for r in range(rows):
+        nz = int(rng.integers(0, min(n, 2 * k + 8) + 1))
+        at = rng.choice(n, nz, replace=False)
+        m[r, at] = rng.integers(1, 4, nz) / 24.0
+    return m
+
+
+@pytest.mark.parametrize("n,k", [(640, 10), (639, 10), (64, 1), (63, 1), (6400, 100), (2000, 31), (70000, 1000),
+                                 (100, 100), (100, 99), (5, 5), (1, 1)])
+def test_oracle_topk_is_torch_topk_on_tie_heavy_rows(n, k):
+    """oracle.topk (libstdc++ restated in C) and the installed torch CPU topk
+    agree bit for bit, ids included, in both libstdc++ regimes: the tie order
+    the device is held to comes from two independent implementations."""
+    from oracle import oracle as orc
+    m = _tie_heavy_rows(n, k, np.random.default_rng(n + k))
+    w, nb = orc.topk(m, k)
+    tw, tn = torch.from_numpy(m).topk(k, 1)
+    assert (w.view(np.uint64) == tw.numpy().view(np.uint64)).all()
+    assert (nb == tn.numpy()).all()
+
+
+@pytest.mark.parametrize("n_hops,k", _SAMPLER_SHAPES)
+def test_oracle_topk_is_torch_topk_on_the_hand_built_rows(n_hops, k):
+    import sampler_util as su
+    from oracle import oracle as orc
+    n_all = su.topk_n_all(k, n_hops)
+    rows = [r for _, r in su.topk_catalogue(n_hops, k)]
+    dense = np.stack([su.dense_from_runs(r, n_all, n_hops) for r in rows])
+    w, nb = orc.topk(dense, k)
+    tw, tn = torch.from_numpy(dense).topk(k, 1)
+    assert (w.view(np.uint64) == tw.numpy().view(np.uint64)).all()
+    assert (nb == tn.numpy()).all()
+    ref = su.topk_reference(rows, n_all, n_hops, k, k, chunk_bytes=8 * n_all * 7)  # chunks of 7 rows
+    assert (ref[0] == w).all() and (ref[1] == nb).all()
+
+
+def test_sampler_checkers_reject_planted_defects():
+    """One defect at a time in a fake device result; each must be rejected
+    with the source index and the column in the message."""
+    import sampler_util as su
+    n_hops, k, t_norm = 24, 10, 4
+    cat = su.topk_catalogue(n_hops, k)
+    rows = [r for _, r in cat][:60]
+    names = [nm for nm, _ in cat][:60]
+    cap = len(rows) + 5
+    runs, n_runs = su.expected_runs(rows, cap, n_hops)
+    su.check_runs("clean", runs, n_runs, rows, n_hops)
+    # self run kept: source 12's own id (one not in its runs) stays in the list
+    s = 12
+    r = rows[s]
+    self_id = int(np.setdiff1d(np.arange(k + 40), r[:, 0])[3])
+    at = int(np.searchsorted(r[:, 0], self_id))
+    kept = np.insert(r, at, [self_id, 1], axis=0)
+    bad_runs, bad_n = su.expected_runs(rows[:s] + [kept] + rows[s + 1:], cap, n_hops)
+    with pytest.raises(AssertionError, match=r"n_runs: source 12 column 0: got \d+, reference \d+"):
+        su.check_runs("self", bad_runs, bad_n, rows, n_hops)
+    with pytest.raises(AssertionError, match=rf"source 12 column {2 * at}: got {self_id},"):
+        su.check_runs("self", bad_runs, n_runs, rows, n_hops)
+    # a run's count off by one
+    s = next(i for i, r in enumerate(rows) if len(r) >= 9)
+    bad_runs = runs.copy()
+    bad_runs[s, 8, 1] += 1
+    with pytest.raises(AssertionError, match=rf"source {s} column 17: got {int(rows[s][8, 1]) + 1}, reference "
+                                             rf"{int(rows[s][8, 1])}; 1 of"):
+        su.check_runs("count", bad_runs, n_runs, rows, n_hops)
+    # a sentinel overwritten past a source's runs, and past the live sources
+    s = next(i for i, r in enumerate(rows) if len(r) == 7)
+    bad_runs = runs.copy()
+    bad_runs[s, 7] = (99, 1)
+    with pytest.raises(AssertionError, match=rf"source {s} column 14: got 99, reference {su.SENT_U32}"):
+        su.check_runs("past", bad_runs, n_runs, rows, n_hops)
+    bad_n = n_runs.copy()
+    bad_n[len(rows) + 2] = 0
+    with pytest.raises(AssertionError, match=rf"n_runs: source {len(rows) + 2} column 0: got 0, reference -1"):
+        su.check_runs("past live", runs, bad_n, rows, n_hops)
+    # top-k outputs
+    n_all = su.topk_n_all(k, n_hops)
+    ref = su.topk_reference(rows, n_all, n_hops, k, t_norm)
+    live = len(rows) - 3
+    want = su.expected_topk(ref, live, cap)
+    clean = lambda: [a.copy() for a in want]
+    su.check_topk("clean", clean(), want)
+    # two tied ids swapped
+    s = names.index("nr24-sparse")
+    w_row = ref[0][s]
+    c = next(j for j in range(k - 1) if w_row[j] == w_row[j + 1])
+    got = clean()
+    got[1][s, [c, c + 1]] = got[1][s, [c + 1, c]]
+    with pytest.raises(AssertionError, match=rf"nb_out: source {s} column {c}: got {int(ref[1][s, c + 1])}, reference "
+                                             rf"{int(ref[1][s, c])}; 2 of"):
+        su.check_topk("swap", got, want)
+    if c < t_norm - 1:
+        got = clean()
+        got[3][s, [c, c + 1]] = got[3][s, [c + 1, c]]
+        with pytest.raises(AssertionError, match=rf"nb32_out: source {s} column {c}:"):
+            su.check_topk("swap32", got, want)
+    # a row shifted by one source
+    got = clean()
+    for a in got:
+        a[1:live] = a[0:live - 1].copy()
+    first = next(i for i in range(1, live) if not np.array_equal(ref[1][i], ref[1][i - 1])
+                 or not np.array_equal(ref[0][i], ref[0][i - 1]))
+    with pytest.raises(AssertionError, match=rf"_out: source {first} column \d+:"):
+        su.check_topk("shift", got, want)
+    # another lane's row sum: the normalised weights of one source scaled
+    s = next(i for i in range(live) if ref[0][i, 0] > 0)
+    got = clean()
+    got[2][s] = got[2][s] * np.float32(0.5)
+    with pytest.raises(AssertionError, match=rf"wn_out: source {s} column 0: got .*0x[0-9a-f]+\), reference"):
+        su.check_topk("rowsum", got, want)
+    # a sentinel overwritten past the live rows; an unwritten live element
+    got = clean()
+    got[0][live + 1, 3] = 0.0
+    with pytest.raises(AssertionError, match=rf"w_out: source {live + 1} column 3: got 0.0 \(0x0\), reference nan \(0x7ff80000deadbeef\)"):
+        su.check_topk("past live", got, want)
+    got = clean()
+    got[2][2, 1] = su.sentinel_array((1,), np.float32)[0]
+    with pytest.raises(AssertionError, match=r"wn_out: source 2 column 1:"):
+        su.check_topk("unwritten", got, want)
+    # a source without runs: the reference's NaN matches a device NaN of any sign, never the sentinel
+    e = names.index("nr0-sparse")
+    assert e < live and np.isnan(ref[2][e]).all()
+    got = clean()
+    got[2][e] = -got[2][e]
+    su.check_topk("nan sign", got, want)
+    got[2][e, 0] = su.sentinel_array((1,), np.float32)[0]
+    with pytest.raises(AssertionError, match=rf"wn_out: source {e} column 0:"):
+        su.check_topk("nan sentinel", got, want)
+
+
+def test_sampler_traces_and_graphs_are_what_the_gpu_tests_assume():
+    """The hand-built traces of the pinsage_visit_topk cases give back their
+    rows (preconditions held, the source outside them), and the walk graphs
+    have the nodes the cases name: a degree-1 item, hubs, the item whose only
+    playlist leads back to it, zero-degree sources and a sink column whose
+    walks the oracle refuses -- with every id inside the graph."""
+    import sampler_util as su
+    for n_all, k in su.VISIT_SHAPES:
+        rng = np.random.default_rng(n_all * 7 + k)
+        rows, src = su.visit_rows(n_all, k, su.VISIT_N_HOPS, rng)
+        assert any(len(r) == 0 for r in rows)
+        if n_all > 2:
+            assert any(len(r) > 1 and len(set(r[:, 1])) == 1 for r in rows)                     # all ties
+            assert any(len(r) > 1 and r[:, 1].max() == su.VISIT_N_HOPS - len(r) + 1 for r in rows)  # one dominant
+        for r, s in zip(rows, src):
+            su.check_row_preconditions(r, su.VISIT_N_HOPS, n_all)
+            tr = su.trace_from_runs(r, s, su.VISIT_N_HOPS, rng)
+            assert tr.dtype == np.int32 and tr.shape == (su.VISIT_N_HOPS,)
+            assert 0 <= tr.min() and tr.max() < n_all
+            assert np.array_equal(su.runs_from_trace(tr, s), r)
+    indptr, indices, n_all, sp = su.bipartite_graph()
+    deg = np.diff(indptr)
+    assert len(indptr) == n_all + 1 and indptr[-1] == len(indices) and 0 <= indices.min() and indices.max() < n_all
+    assert deg.min() == 1 and deg.max() >= 290 and deg[0] >= 290 and deg[n_all - 1] >= 1
+    lo = sp["loner"]
+    pl = indices[indptr[lo]:indptr[lo + 1]]
+    assert len(pl) == 1 and indices[indptr[pl[0]]:indptr[pl[0] + 1]].tolist() == [lo]
+    tr = su.oracle_traces(indptr, indices, [lo, 0], 70, np.float32(0.0), seed=1)
+    assert (tr[0] == lo).all() and len(su.runs_from_trace(tr[1], 0)) > 4
+    indptr, indices, n_all, _ = su.two_item_graph()
+    tr = su.oracle_traces(indptr, indices, [0, 1, 2], 200, np.float32(0.5), seed=2)
+    assert set(tr[0]) == {0, 1} and set(tr[2]) == {2}
+    for name, indptr, indices, n_all, sources, bad in su.zero_degree_graphs():
+        assert len(indptr) == n_all + 1 and indices.max() < n_all and sources.max() < n_all and sources.min() >= 0
+        for alpha in (0.0, 1.0):
+            tr = su.oracle_traces(indptr, indices, sources, 9, np.float32(alpha), seed=3)
+            assert [i for i, t in enumerate(tr) if t is None] == bad, name
+        rows = su.oracle_runs(tr, sources)
+        runs, n_runs = su.expected_runs(rows, len(sources), 9)
+        assert all(n_runs[i] == 0 for i in bad) and (runs[bad] == su.SENT_U32).all()
