@@ -179,6 +179,10 @@ _SIGS = {
     "pinsage_list_intra_sim": (ctypes.c_int, [vp, i64, i64, i64, vp, vp, i64, i64, i64, vp, vp, vp]),
     "pinsage_list_overlap_max_k": (i64, []),
     "pinsage_list_pair_overlap": (ctypes.c_int, [vp, i64, i64, i64, i64, vp, i64, vp, vp, vp]),
+    "pinsage_cooc_tile": (i64, []),
+    "pinsage_cooc_scratch_bytes": (i64, [i64, i64]),
+    "pinsage_cooc_counts": (ctypes.c_int, [vp, vp, vp, vp, i64, i64, vp, i64, vp, vp, vp]),
+    "pinsage_cooc_jaccard": (ctypes.c_int, [vp, vp, vp, vp, i64, i64, vp, i64, i64, vp, i64, vp, vp, vp, vp]),
     "pinsage_engine_create": (ctypes.c_int, [ctypes.POINTER(EngineConfig), ctypes.POINTER(vp)]),
     "pinsage_engine_destroy": (None, [vp]),
     "pinsage_engine_live_count": (i64, []),

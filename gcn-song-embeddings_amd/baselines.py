@@ -11,6 +11,14 @@ building any list; and the beyond-accuracy metrics of eval.py:255-374 and
 :445-467 (intra- and inter-list diversity, coverage, average degree) over a
 kNN id matrix, the two diversities on the kernels of csrc/listmetrics.hip.
 
+``JaccardFast`` (baselines.py:194-220), the co-occurrence baseline, runs on the
+kernels of csrc/cooc.hip: count rows of the playlist-track product per batch of
+queries (never the n x n product), scored and selected by the cosine path's
+selection kernel under a Jaccard key.  With it, ``Random`` (baselines.py:
+380-397), ``low_co_accuracy`` (eval.py:391-406), ``LazyKnnDict`` (eval.py:
+177-215) and ``compute_results_table`` (eval.py:413-443) the reference's main
+results table is produced from this package.
+
 The reference's other baseline recommenders (node2vec, implicit ALS,
 networkx similarities, lib/gnns) are out of scope; their libraries are not
 part of this build.  Names, signatures, return types and RNG consumption
@@ -269,6 +277,100 @@ def low_degree_accuracy_from_ranks(ranks, g, test_positives, K, degree_thr, acc_
     return acc_func(r[keep.to(r.device)], K)
 
 
+def _low_co_selection(test_positives, co_thr, queries, n_nodes):
+    """eval.py:393-403: which pairs have a query among the candidate nodes with
+    at most co_thr held-out pairs.  The reference sums the rows of a track-track
+    matrix it builds from test_positives alone: that sum is the number of pairs
+    the node is the query of."""
+    tp = _pairs(test_positives).cpu()
+    co_counts = torch.bincount(tp[:, 0], minlength=int(n_nodes))[queries]
+    return torch.isin(tp[:, 0], queries[co_counts <= co_thr])
+
+
+def low_co_accuracy(knn_mat, g, test_positives, K, co_thr, acc_func, queries=None, track_ids=None):
+    """eval.py:391-406: ``acc_func(knn_mat, pairs, K)`` (hit_rate or mrr) over the
+    pairs whose query occurs as a query in at most co_thr pairs of
+    test_positives.  ``g`` and ``track_ids`` are accepted and unused, as in the
+    reference.  If no pair is kept acc_func divides by zero, as in the reference."""
+    n = int(torch.as_tensor(knn_mat).shape[0])
+    if queries is None:
+        queries = torch.arange(0, n, dtype=torch.int64)
+    keep = _low_co_selection(test_positives, co_thr, queries, n)
+    return acc_func(knn_mat, _pairs(test_positives)[keep.to(_pairs(test_positives).device)], K)
+
+
+def low_co_accuracy_from_ranks(ranks, test_positives, K, co_thr, acc_func, queries=None, n_nodes=None):
+    """``low_co_accuracy`` from rank_from_emb's ranks of test_positives:
+    ``acc_func(ranks_of_the_kept_pairs, K)`` with hit_rate_from_ranks or
+    mrr_from_ranks.  The candidate nodes are ``queries``, else all n_nodes
+    (default: one more than the largest id in test_positives)."""
+    tp = _pairs(test_positives)
+    if n_nodes is None:
+        n_nodes = int(tp.max()) + 1 if tp.numel() else 0
+    if queries is None:
+        queries = torch.arange(0, int(n_nodes), dtype=torch.int64)
+    keep = _low_co_selection(test_positives, co_thr, queries, n_nodes)
+    r = torch.as_tensor(ranks).reshape(-1)
+    return acc_func(r[keep.to(r.device)], K)
+
+
+class LazyKnnDict:
+    """eval.py:177-215: the saved kNN lists of several models, each loaded from
+    its ``save_knn`` file when asked for.  Iterating yields the model names."""
+
+    def __init__(self, model_names, ids, save_dir):
+        self.all_nodes = torch.arange(0, len(ids), dtype=torch.int64)
+        self.models = model_names
+        self.save_dir = save_dir
+        self.idx = 0
+        self.times = {m_name: None for m_name in model_names}
+
+    def __getitem__(self, m_name):
+        tup = load_knn(m_name, self.all_nodes, self.save_dir)
+        return tup[0], tup[1].to(torch.int64)
+
+    def get_times(self, m_name):
+        """(train, embed, knn) seconds of the model's file; zeros for a file
+        saved without them."""
+        if not self.times[m_name]:
+            tpl = load_knn(m_name, self.all_nodes, self.save_dir)
+            self.times[m_name] = tuple(tpl[2:5]) if len(tpl) == 5 else (0, 0, 0)
+        return self.times[m_name]
+
+    def __len__(self):
+        return len(self.models)
+
+    def __iter__(self):
+        self.idx = 0
+        return self
+
+    def __next__(self):
+        if self.idx >= len(self):
+            raise StopIteration
+        self.idx += 1
+        return self.models[self.idx - 1]
+
+
+def compute_results_table(knn_dict, test_positives, g, times=True, degree_thr=1):
+    """eval.py:413-443: the accuracy metrics of every model of knn_dict (a
+    LazyKnnDict, or any mapping name -> (weights, id matrix) that also answers
+    ``get_times`` when ``times`` is set) as a pandas.DataFrame with the
+    reference's columns in the reference's order."""
+    import pandas as pd
+    results = {}
+    for model in knn_dict:
+        _, knn_mat = knn_dict[model]
+        row = {f"hr (k={k})": hit_rate(knn_mat, test_positives, k) for k in (10, 100, 500)}
+        row["mrr"] = mrr(knn_mat, test_positives, 1000, 1)
+        row["low-degree accuracy"] = low_degree_accuracy(knn_mat, g, test_positives, 1000, degree_thr=degree_thr,
+                                                         acc_func=mrr)
+        row["low-co accuracy"] = low_co_accuracy(knn_mat, g, test_positives, 1000, co_thr=1, acc_func=mrr)
+        if times:
+            row["t (train)"], row["t (emb)"], row["t (knn)"] = knn_dict.get_times(model)
+        results[model] = row
+    return pd.DataFrame.from_dict(results, orient="index")
+
+
 # ----------------------------------------------------------------------------- beyond-accuracy metrics
 # eval.py:271-374 and :445-467.  knn_mat is the id matrix of knn_from_emb /
 # load_knn ([n queries, list_len]), on any device and of any integer dtype;
@@ -454,6 +556,128 @@ class PersPageRank(PredictionModel):
         return psm.sample_neighborhood_topt(self.g, None, nodeset, self.n_hops, self.alpha, k)
 
 
+class JaccardFast(PredictionModel):
+    """Nearest neighbours by the Jaccard similarity of the tracks' collection
+    sets (baselines.py:194-220):  |C(q) & C(t)| / (|C(q) | C(t)| + 1e-10).
+
+    The reference forms the n_tracks x n_tracks product of the collection-track
+    matrix with its transpose in scipy and densifies rows of it per query batch
+    on the host.  Here ``train`` builds the two membership CSRs on the GPU once
+    and ``knn`` counts, scores and selects per batch of queries in HIP
+    (csrc/cooc.hip + the selection kernel of csrc/knn.hip); nothing n x n exists.
+
+    Scores equal the reference's bit for bit.  The ORDER among equal scores is
+    documented here (score descending, then id ascending; a list with fewer than
+    k non-zero scores is filled with the lowest zero-score ids), while the
+    reference's is whatever ``torch.topk`` does: on the 300-track graph of
+    tests/golden/jaccard.npz (a hub, duplicate edges, tracks in no collection)
+    6 % of the id cells coincide at k = 50.  Column 0, which ``knn`` drops as the
+    reference does, is the query itself only where no track of a lower id has
+    the same collection set and the query is in a collection at all (53 % of the
+    rows of that graph)."""
+
+    def __init__(self):
+        pass
+
+    def train(self, g, ids, train_set, test_set, features):
+        """Nodes [0, len(ids)) of g are tracks, the rest collections.  Every edge
+        with exactly one track endpoint is a membership, whichever way it points
+        and however often it is stored (the reference takes the set
+        successors | predecessors per collection); an edge between two tracks is
+        ignored, one between two collections raises ValueError (the reference's
+        matrix assignment raises on the column index)."""
+        nat.require_gpu()
+        self.ids = ids
+        self.n = n_tracks = len(ids)
+        self.n_cols = n_cols = len(g) - n_tracks
+        if n_tracks < 1 or n_cols < 0:
+            raise ValueError(f"JaccardFast: {n_tracks} tracks in a graph of {len(g)} nodes")
+        dev = nat.device()
+        indptr, indices = g.device_csr(dev)
+        src = torch.repeat_interleave(torch.arange(len(g), dtype=torch.int64, device=dev), indptr[1:] - indptr[:-1])
+        dst = indices.to(torch.int64)
+        s_tr, d_tr = src < n_tracks, dst < n_tracks
+        if bool((~s_tr & ~d_tr).any()):
+            raise ValueError("JaccardFast: an edge joins two collections")
+        keep = s_tr ^ d_tr
+        track = torch.where(s_tr, src, dst)[keep]
+        col = torch.where(s_tr, dst, src)[keep] - n_tracks
+        # one 64-bit key per membership: unique() removes duplicates and sorts the rows
+        tc = torch.unique(track * max(n_cols, 1) + col)
+        ct = torch.unique(col * n_tracks + track)
+        self._t2c = self._csr(tc // max(n_cols, 1), tc % max(n_cols, 1), n_tracks)
+        self._c2t = self._csr(ct // n_tracks, ct % n_tracks, n_cols)
+        self.nbh_sizes = self._t2c[0][1:] - self._t2c[0][:-1]  # int64 [n_tracks], on the GPU
+
+    @staticmethod
+    def _csr(rows, cols, n_rows):
+        ptr = torch.zeros(n_rows + 1, dtype=torch.int64, device=rows.device)
+        torch.cumsum(torch.bincount(rows, minlength=n_rows), 0, out=ptr[1:])
+        return ptr, cols.to(torch.int32).contiguous()
+
+    def _queries(self, nodeset):
+        qs = torch.as_tensor(nodeset).reshape(-1).to(torch.int64)
+        if qs.numel() and (int(qs.min()) < 0 or int(qs.max()) >= self.n):
+            raise IndexError(f"JaccardFast: query ids out of range for {self.n} tracks")
+        return qs.to("cuda").contiguous()
+
+    def _csr_args(self):
+        return (nat.ptr(self._t2c[0]), nat.ptr(self._t2c[1]), nat.ptr(self._c2t[0]), nat.ptr(self._c2t[1]),
+                self.n, self.n_cols)
+
+    def intersect_sizes(self, nodeset):
+        """Rows ``nodeset`` of the reference's ``intersect_sizes`` matrix, dense:
+        int32 [len(nodeset), n_tracks] on the GPU."""
+        qd = self._queries(nodeset)
+        nq = int(qd.numel())
+        out = torch.empty((nq, self.n), dtype=torch.int32, device="cuda")
+        err = torch.zeros(1, dtype=torch.int32, device="cuda")
+        nat.check(nat.lib().pinsage_cooc_counts(*self._csr_args(), nat.ptr(qd), nq, nat.ptr(out), nat.ptr(err),
+                                                nat.stream_ptr()), "cooc_counts")
+        if int(err):
+            raise IndexError(f"JaccardFast: query ids out of range for {self.n} tracks")
+        return out
+
+    def knn(self, nodeset, k):
+        """The reference's ``torch.topk(scores, k)`` with column 0 dropped:
+        (float32 [nq, k - 1], int64 [nq, k - 1]) on nodeset's device, k - 1
+        columns (not k, as knn_from_emb returns)."""
+        out_dev = torch.as_tensor(nodeset).device
+        qd = self._queries(nodeset)
+        nq, k, n = int(qd.numel()), int(k), self.n
+        w = torch.empty((nq, k), dtype=torch.float32, device="cuda")
+        nb = torch.empty((nq, k), dtype=torch.int64, device="cuda")
+        if nq:
+            L = nat.lib()
+            rows = max(1, min(nq, (KNN_SCRATCH_BYTES - 8 * n) // max(1, 4 * n)))
+            nbytes = L.pinsage_cooc_scratch_bytes(n, rows)
+            scratch = torch.empty(nbytes, dtype=torch.uint8, device="cuda")
+            err = torch.zeros(1, dtype=torch.int32, device="cuda")
+            nat.check(L.pinsage_cooc_jaccard(*self._csr_args(), nat.ptr(qd), nq, k, nat.ptr(scratch), nbytes,
+                                             nat.ptr(w), nat.ptr(nb), nat.ptr(err), nat.stream_ptr()),
+                      "cooc_jaccard")
+            if int(err):
+                raise IndexError(f"JaccardFast: query ids out of range for {n} tracks")
+        return w[:, 1:].to(out_dev), nb[:, 1:].to(out_dev)
+
+
+class Random(PredictionModel):
+    """Random recommendations (baselines.py:380-397): per query the first k of
+    a ``torch.randperm(n)`` from torch's global generator, weights of ones (int64,
+    as ``ones_like`` of the ids gives).  Host only."""
+
+    def __init__(self):
+        pass
+
+    def train(self, g, ids, train_set, test_set, features):
+        self.ids = ids
+        self.n = len(ids)
+
+    def knn(self, nodeset, k):
+        nodes = torch.stack([torch.randperm(self.n)[0:k] for _ in range(nodeset.shape[0])], dim=0)
+        return torch.ones_like(nodes), nodes
+
+
 class EmbeddingTable(EmbeddingModel):
     """kNN over a fixed embedding table (e.g. PinSage.embed output): the
     embed/knn pair of the reference's EmbeddingModel wrappers
@@ -503,4 +727,6 @@ __all__ = ["PRECOMP_K", "PredictionModel", "EmbeddingModel", "cosine_sim_ab", "k
            "PersPageRank", "EmbeddingTable", "save_knn", "load_knn", "RANK_MAX_GROUP", "rank_from_emb",
            "hit_rate", "mrr", "hit_rate_from_ranks", "mrr_from_ranks", "low_degree_accuracy",
            "low_degree_accuracy_from_ranks", "LIST_OVERLAP_MAX_K", "intra_diversity", "inter_diversity",
-           "coverage", "average_degree", "degree_dist", "beyond_accuracy", "compute_beyond_accuracy_table"]
+           "coverage", "average_degree", "degree_dist", "beyond_accuracy", "compute_beyond_accuracy_table",
+           "JaccardFast", "Random", "low_co_accuracy", "low_co_accuracy_from_ranks", "LazyKnnDict",
+           "compute_results_table"]

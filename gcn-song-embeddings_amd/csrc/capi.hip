@@ -11,6 +11,7 @@
 #include "aggw.h"
 #include "capi.h"
 #include "conv.h"
+#include "cooc.h"
 #include "fly.h"
 #include "frontier.h"
 #include "gemm.h"
@@ -731,6 +732,27 @@ int pinsage_linear_split_b(const float* A, int64_t lda, const int32_t* a_idx, in
   p.stream_k = 0;
   p.prec = 1;
   return launch_gemm(p, (hipStream_t)stream);
+}
+
+int64_t pinsage_cooc_tile(void) { return cooc_tile(); }
+
+int64_t pinsage_cooc_scratch_bytes(int64_t n_tracks, int64_t batch_rows) {
+  return cooc_scratch_bytes(n_tracks, batch_rows < 1 ? 1 : batch_rows);
+}
+
+int pinsage_cooc_counts(const int64_t* t2c_ptr, const int32_t* t2c_idx, const int64_t* c2t_ptr,
+                        const int32_t* c2t_idx, int64_t n_tracks, int64_t n_cols, const int64_t* queries,
+                        int64_t nq, int32_t* out, int* err, void* stream) {
+  return launch_cooc_counts(t2c_ptr, t2c_idx, c2t_ptr, c2t_idx, n_tracks, n_cols, queries, nq, out, err,
+                            (hipStream_t)stream);
+}
+
+int pinsage_cooc_jaccard(const int64_t* t2c_ptr, const int32_t* t2c_idx, const int64_t* c2t_ptr,
+                         const int32_t* c2t_idx, int64_t n_tracks, int64_t n_cols, const int64_t* queries,
+                         int64_t nq, int64_t k, void* scratch, int64_t scratch_bytes, float* out_w, int64_t* out_n,
+                         int* err, void* stream) {
+  return launch_cooc_jaccard(t2c_ptr, t2c_idx, c2t_ptr, c2t_idx, n_tracks, n_cols, queries, nq, k, scratch,
+                             scratch_bytes, out_w, out_n, err, (hipStream_t)stream);
 }
 
 int64_t pinsage_knn_scratch_bytes(int64_t n, int64_t batch_rows) {

@@ -14,6 +14,18 @@ int launch_knn_cosine(const float* emb, int64_t n, int64_t d, int64_t ld, const 
                       int64_t k, float eps, void* scratch, int64_t scratch_bytes, float* out_w, int64_t* out_n,
                       int* err, hipStream_t st);
 
+// largest k of any selection here (kKnnMaxK)
+int knn_max_k();
+
+// The same selection over Jaccard scores (cooc.hip's second half): row b of
+// counts int32 [m][n] holds the co-occurrence counts of a query of degree
+// qdeg[b] with every track, deg int32 [n] the tracks' degrees;
+//   s(b, t) = float(co) / (float(qdeg[b] + deg[t] - co) + 1e-10f)   (fp32, IEEE division)
+// out_w / out_n [m][k]: the k largest, sorted (s desc, index asc).  counts must
+// be 16-byte aligned when n % 4 == 0, and so must deg; m <= 65535.
+int launch_knn_select_jaccard(const int32_t* counts, int64_t n, const int32_t* deg, const int32_t* qdeg, int64_t m,
+                              int64_t k, float* out_w, int64_t* out_n, hipStream_t st);
+
 // scratch bytes for rank batches of qb query rows over n table rows
 int64_t rank_scratch_bytes(int64_t n, int64_t qb);
 // most targets one query row may own (kRankMaxGroup)

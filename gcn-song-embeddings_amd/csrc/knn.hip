@@ -18,6 +18,10 @@
 // index asc).  The row of dot products stays in the Infinity Cache across the
 // select's four passes when the batch is sized to it.
 //
+// The selection kernel is a template over a key policy (what a row holds and
+// how a key is made of it): cosine over dot products here, Jaccard over the
+// co-occurrence counts of cooc.hip (launch_knn_select_jaccard).
+//
 // The ranks of given rows in that order (the positives of held-out pairs:
 // eval.py:227-250 hit_rate / mrr) are counted without any list by
 // rank_count_kernel at the end of this file, over the same dot products,
@@ -44,6 +48,40 @@ __device__ __forceinline__ float key2f(uint32_t k) {
 __device__ __forceinline__ uint32_t knn_key(float dot, float na, float nj, float eps) {
   return f2key(dot / __fadd_rn(__fmul_rn(na, nj), eps));
 }
+
+// What knn_select_kernel orders a row by.  A policy names the row's element
+// type, the per-column array it is paired with and the per-row scalar, and turns
+// one (row value, column value, row scalar) into a key.  kFloor: no key is below
+// kFloorKey (a row may consist almost wholly of it).
+struct KnnCosineKey {  // row of dot products, norms[], |q|
+  using Row = float;
+  using Row4 = float4;
+  using Col = float;
+  using Col4 = float4;
+  using Scalar = float;
+  static constexpr bool kFloor = false;
+  static constexpr uint32_t kFloorKey = 0u;
+  float eps;
+  __device__ __forceinline__ uint32_t operator()(float dot, float nj, float na) const {
+    return knn_key(dot, na, nj, eps);
+  }
+};
+// Jaccard similarity of two tracks' collection sets (baselines.py:211-217):
+// row of co-occurrence counts, deg[], deg[q];  co / (union + 1e-10) as torch
+// computes it over int32 tensors and a Python float: the union is rounded to
+// fp32, 1e-10 vanishes unless the union is 0, IEEE division.
+struct KnnJaccardKey {
+  using Row = int32_t;
+  using Row4 = int4;
+  using Col = int32_t;
+  using Col4 = int4;
+  using Scalar = int32_t;
+  static constexpr bool kFloor = true;
+  static constexpr uint32_t kFloorKey = 0x80000000u;  // f2key(0.0f): scores are >= 0
+  __device__ __forceinline__ uint32_t operator()(int32_t co, int32_t dj, int32_t dq) const {
+    return f2key((float)co / __fadd_rn((float)(dq + dj - co), 1e-10f));
+  }
+};
 
 __global__ void knn_row_norms_kernel(const float* __restrict__ e, int64_t n, int d, int64_t ld,
                                      float* __restrict__ norms) {
@@ -154,10 +192,15 @@ __device__ uint32_t knn_lds_kth(Get get, int cnt, uint32_t rank, uint32_t* hist,
   return prefix;
 }
 
+template <class KP>
 __global__ __launch_bounds__(kKnnBlock) void knn_select_kernel(
-    const float* __restrict__ dots, int64_t n, const float* __restrict__ norms,
-    const float* __restrict__ qn, float eps, int k, int P, float* __restrict__ out_w,
+    const typename KP::Row* __restrict__ dots, int64_t n, const typename KP::Col* __restrict__ norms,
+    const typename KP::Scalar* __restrict__ qn, KP kp, int k, int P, float* __restrict__ out_w,
     int64_t* __restrict__ out_n) {
+  using Row = typename KP::Row;
+  using Col = typename KP::Col;
+  using Row4 = typename KP::Row4;
+  using Col4 = typename KP::Col4;
   __shared__ uint32_t hist[4096];
   __shared__ uint32_t skey[kKnnMaxK];
   __shared__ int32_t sidx[kKnnMaxK];
@@ -167,13 +210,11 @@ __global__ __launch_bounds__(kKnnBlock) void knn_select_kernel(
 
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   const int64_t b = blockIdx.x;
-  const float* row = dots + b * n;
-  const float na = qn[b];
-  auto key_of = [&](float dot, float nj) __attribute__((always_inline)) {
-    return knn_key(dot, na, nj, eps);
-  };
+  const Row* row = dots + b * n;
+  const typename KP::Scalar na = qn[b];
+  auto key_of = [&](Row dot, Col nj) __attribute__((always_inline)) { return kp(dot, nj, na); };
   auto key_at = [&](int64_t j) __attribute__((always_inline)) { return key_of(row[j], norms[j]); };
-  // rows of n % 4 == 0 floats start 16-byte aligned (the dot rows are n apart)
+  // rows of n % 4 == 0 elements start 16-byte aligned (the rows are n apart)
   const bool vec = (n % 4) == 0;
 
   // ---- one pass.  A threshold t = a key of the row's leading kKnnSample keys
@@ -196,6 +237,11 @@ __global__ __launch_bounds__(kKnnBlock) void knn_select_kernel(
     const uint32_t r = S == n ? (uint32_t)k : (uint32_t)min<double>(S, er * 1.5 + 4.0 * sqrt(er) + 8.0);
     uint32_t dummy;
     const uint32_t t = knn_lds_kth([&](int i) { return skey[i]; }, S, r, hist, sh2, &dummy);
+    // a floor threshold over more keys than the segments hold: every key passes
+    // it and some segment overflows, so the pass visits nothing and reports a
+    // full segment (block-uniform; never taken by a policy without a floor)
+    const bool doomed = KP::kFloor && t == KP::kFloorKey && n > 16 * kKnnSeg;
+    const int64_t np = doomed ? 0 : n;
     int cw = 0;  // this wave's candidates (wave-uniform)
     bool over = false;
     uint32_t* const wk = ckey + wv * kKnnSeg;
@@ -213,16 +259,17 @@ __global__ __launch_bounds__(kKnnBlock) void knn_select_kernel(
       cw += __popcll(m);
     };
     // block-uniform trip counts: take() uses wave-wide ballots
-    const int64_t n16 = vec ? (n / 16) * 16 : 0;
+    const int64_t n16 = vec ? (np / 16) * 16 : 0;
     for (int64_t base = 0; base < n16; base += (int64_t)kKnnBlock * 16) {
       const int64_t j0 = base + (int64_t)tid * 16;
       const bool ok = j0 < n16;
       const int64_t jl = ok ? j0 : 0;
-      float4 dv[4], nv[4];
+      Row4 dv[4];
+      Col4 nv[4];
 #pragma unroll
       for (int u = 0; u < 4; ++u) {
-        dv[u] = *reinterpret_cast<const float4*>(row + jl + 4 * u);
-        nv[u] = *reinterpret_cast<const float4*>(norms + jl + 4 * u);
+        dv[u] = *reinterpret_cast<const Row4*>(row + jl + 4 * u);
+        nv[u] = *reinterpret_cast<const Col4*>(norms + jl + 4 * u);
       }
 #pragma unroll
       for (int u = 0; u < 4; ++u) {
@@ -232,11 +279,11 @@ __global__ __launch_bounds__(kKnnBlock) void knn_select_kernel(
         take(key_of(dv[u].w, nv[u].w), j0 + 4 * u + 3, ok);
       }
     }
-    for (int64_t j0 = n16; j0 < n; j0 += kKnnBlock) {
+    for (int64_t j0 = n16; j0 < np; j0 += kKnnBlock) {
       const int64_t j = j0 + tid;
-      take(j < n ? key_at(j) : 0u, j, j < n);
+      take(j < np ? key_at(j) : 0u, j, j < np);
     }
-    over = cw > kKnnSeg;
+    over = doomed || cw > kKnnSeg;
     if (lane == 0) seg_cnt[wv] = over ? -1 : cw;
     __syncthreads();
     int tot = 0;
@@ -300,18 +347,26 @@ __global__ __launch_bounds__(kKnnBlock) void knn_select_kernel(
     for (int i = tid; i < nb; i += kKnnBlock) hist[i] = 0;
     __syncthreads();
     const int hs = sh + widths[p];  // bits above this digit must equal the prefix
+    // keys at the policy's floor (most of a sparse row: one bin) are counted in
+    // a register and added once per thread
+    uint32_t n_floor = 0;
     auto count = [&](uint32_t key) __attribute__((always_inline)) {
+      if (KP::kFloor && key == KP::kFloorKey) {
+        ++n_floor;
+        return;
+      }
       if (hs >= 32 || (key >> hs) == prefix) atomicAdd(&hist[(key >> sh) & (nb - 1)], 1u);
     };
     // 4 x 16-byte loads of dots and norms in flight per thread (the row is
     // streamed four times: memory-level parallelism, not LDS, bounds a pass)
     const int64_t n16 = vec ? (n / 16) * 16 : 0;
     for (int64_t j0 = (int64_t)tid * 16; j0 < n16; j0 += (int64_t)kKnnBlock * 16) {
-      float4 dv[4], nv[4];
+      Row4 dv[4];
+      Col4 nv[4];
 #pragma unroll
       for (int u = 0; u < 4; ++u) {
-        dv[u] = *reinterpret_cast<const float4*>(row + j0 + 4 * u);
-        nv[u] = *reinterpret_cast<const float4*>(norms + j0 + 4 * u);
+        dv[u] = *reinterpret_cast<const Row4*>(row + j0 + 4 * u);
+        nv[u] = *reinterpret_cast<const Col4*>(norms + j0 + 4 * u);
       }
 #pragma unroll
       for (int u = 0; u < 4; ++u) {
@@ -322,6 +377,8 @@ __global__ __launch_bounds__(kKnnBlock) void knn_select_kernel(
       }
     }
     for (int64_t j = n16 + tid; j < n; j += kKnnBlock) count(key_at(j));
+    if (KP::kFloor && n_floor && (hs >= 32 || (KP::kFloorKey >> hs) == prefix))
+      atomicAdd(&hist[(KP::kFloorKey >> sh) & (nb - 1)], n_floor);
     __syncthreads();
     if (wv == 0) {  // scan bins from the top: the bin holding the need-th largest
       const int per = nb / 64;
@@ -464,10 +521,25 @@ int launch_knn_cosine(const float* emb, int64_t n, int64_t d, int64_t ld, const 
     p.c = dots;
     p.ldc = n;
     PS_TRY(launch_gemm(p, st));
-    hipLaunchKernelGGL(knn_select_kernel, dim3((unsigned)m), dim3(kKnnBlock), 0, st, dots, n, norms,
-                       qn, eps, (int)k, P, out_w + q0 * k, out_n + q0 * k);
+    hipLaunchKernelGGL(knn_select_kernel<KnnCosineKey>, dim3((unsigned)m), dim3(kKnnBlock), 0, st, dots, n,
+                       norms, qn, KnnCosineKey{eps}, (int)k, P, out_w + q0 * k, out_n + q0 * k);
     PS_CHECK_LAUNCH();
   }
+  return kOk;
+}
+
+int knn_max_k() { return kKnnMaxK; }
+
+int launch_knn_select_jaccard(const int32_t* counts, int64_t n, const int32_t* deg, const int32_t* qdeg, int64_t m,
+                              int64_t k, float* out_w, int64_t* out_n, hipStream_t st) {
+  PS_REQUIRE(n > 0 && n <= INT32_MAX && m >= 0 && m <= 65535, kErrArg, "knn: bad sizes");
+  PS_REQUIRE(k >= 1 && k <= n && k <= kKnnMaxK, kErrArg, "knn: need 1 <= k <= min(n, 4096)");
+  if (m == 0) return kOk;
+  int P = 64;
+  while (P < k) P <<= 1;
+  hipLaunchKernelGGL(knn_select_kernel<KnnJaccardKey>, dim3((unsigned)m), dim3(kKnnBlock), 0, st, counts, n, deg,
+                     qdeg, KnnJaccardKey{}, (int)k, P, out_w, out_n);
+  PS_CHECK_LAUNCH();
   return kOk;
 }
 

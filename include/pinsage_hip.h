@@ -761,6 +761,51 @@ int64_t pinsage_list_overlap_max_k(void);
 int pinsage_list_pair_overlap(const int64_t* lists, int64_t nq, int64_t ldk, int64_t kc, int64_t n_ids,
                               const int64_t* pairs, int64_t np, int32_t* out, int* err, void* stream);
 
+/* ------------------------------------------------------------------ Jaccard co-occurrence neighbours
+ * JaccardFast (baselines.py:194-220) without its n_tracks x n_tracks scipy
+ * product.  The playlist-track membership relation is given as two CSRs with
+ * duplicates removed (device arrays):
+ *   t2c_ptr int64 [n_tracks + 1], t2c_idx int32: the collections of each track,
+ *     ids in [0, n_cols);
+ *   c2t_ptr int64 [n_cols + 1],  c2t_idx int32: the tracks of each collection,
+ *     ids in [0, n_tracks), ASCENDING within a row (the kernel binary-searches).
+ * deg[t] = t2c_ptr[t + 1] - t2c_ptr[t] is the reference's nbh_sizes.
+ *
+ * pinsage_cooc_counts: out int32 [nq][n_tracks],
+ *   out[i][t] = #{ c : queries[i] in c and t in c },
+ * the rows intersect_sizes[nodeset, :].toarray() of the reference.  The track
+ * range is tiled through LDS in tiles of pinsage_cooc_tile() counters; every
+ * element of out is written exactly once (no memset is needed) and the counts
+ * are integer adds: two runs give the same bits.
+ *
+ * pinsage_cooc_jaccard: for each query q
+ *   s(q, t) = float(co) / (float(deg[q] + deg[t] - co) + 1e-10f),  t in [0, n_tracks)
+ * in fp32 with IEEE division, which is what torch computes for the reference's
+ * intersect / (union + 1e-10) over int32 tensors (two tracks in no collection
+ * score 0).  out_w f32 [nq][k] / out_n int64 [nq][k]: the k largest, sorted
+ * descending, exact ties by ascending id (pinsage_knn_cosine's order and
+ * selection kernel); a row with fewer than k non-zero scores is filled with the
+ * lowest zero-score ids.  The reference then drops column 0.
+ * 1 <= k <= min(n_tracks, 4096), n_tracks < 2^31.  scratch: 16-byte aligned
+ * device bytes >= pinsage_cooc_scratch_bytes(n_tracks, rows) for some batch of
+ * rows >= 1 (the int32 count rows of one batch of queries live there).
+ *
+ * queries int64 [nq] (device).  err (nullable): a device int set to 1 when a
+ * query id is outside [0, n_tracks); the id is clamped so that no access
+ * strays, and the caller raises.  A refused call (PINSAGE_ERR_ARG: a size out
+ * of range, k outside its bounds, a null pointer other than err and the index
+ * arrays of an empty relation; PINSAGE_ERR_WORKSPACE: scratch below one row)
+ * returns before any launch and leaves the outputs untouched. */
+int64_t pinsage_cooc_tile(void);
+int64_t pinsage_cooc_scratch_bytes(int64_t n_tracks, int64_t batch_rows);
+int pinsage_cooc_counts(const int64_t* t2c_ptr, const int32_t* t2c_idx, const int64_t* c2t_ptr,
+                        const int32_t* c2t_idx, int64_t n_tracks, int64_t n_cols, const int64_t* queries,
+                        int64_t nq, int32_t* out, int* err, void* stream);
+int pinsage_cooc_jaccard(const int64_t* t2c_ptr, const int32_t* t2c_idx, const int64_t* c2t_ptr,
+                         const int32_t* c2t_idx, int64_t n_tracks, int64_t n_cols, const int64_t* queries,
+                         int64_t nq, int64_t k, void* scratch, int64_t scratch_bytes, float* out_w, int64_t* out_n,
+                         int* err, void* stream);
+
 /* ------------------------------------------------------------------ train-step engine
  * PinSageModel.forward / PinSage.train_batch (pinsage_model.py:246-265,
  * pinsage_training.py:181-214) with device-resident sizes.  Parameters live in
