@@ -133,10 +133,6 @@ struct DqChunkParams {
   int hid = 0;
   float* dpq = nullptr;
   float* part = nullptr;  // [max_chunks][hid] chunk partials
-  // chunk rows (csrc set, needs q_src): masked partials stay in part, no
-  // combine; csrc[chunk] = q_src of the chunk's row
-  const int32_t* q_src = nullptr;
-  int32_t* csrc = nullptr;
   // split-row tree (cbase and tk set, hid <= 512): split rows combined by their
   // own chunks, no combine launch; tk: dq_tree_levels x max_chunks zeroed ints
   const int* cbase = nullptr;

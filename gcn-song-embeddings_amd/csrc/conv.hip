@@ -721,13 +721,10 @@ __global__ __launch_bounds__(1024) void csr_sort_rows_kernel(const int2* __restr
 // dq_combine_kernel sums them in chunk order (deterministic, and no
 // device-scope float atomics: with per-XCD L2s those run at the memory side
 // and serialise on popular rows).
+// (A chunk-rows form -- every chunk's masked partial kept as its own row of
+// the bottom layer's Q weight gradient GEMM, no combine -- measured even, C2
+// 0.451 -> 0.454 ms/step, C4 0.483 -> 0.476, and was removed.)
 //
-// CM (chunk rows, the bottom layer): every chunk writes its MASKED partial,
-// lrelu'(q[u]) * sum over its occurrences, to part[ci] and its row's source
-// index q_src[u] to csrc[ci].  The mask is elementwise, so u's masked partials
-// add up to dpq[u]; the Q weight gradient dpq^T h[q_src] is then the same
-// GEMM over chunk rows (h gathered through csrc) and no combine is needed --
-// at the bottom layer nothing else reads dpq (no dh below the input features).
 // Row-granular write-through store / L2-bypassing load of one float4 of a
 // partial row (the split-row tree below: a partial written on one XCD is read
 // by a wave on another, and the XCDs' L2s are not coherent; the same hand-off
@@ -842,12 +839,11 @@ __device__ __forceinline__ void dq_tree_leaf(float4 (&acc)[VEC], const float4 (&
 // PL3 (with TREE; the bottom layer, where only the Q weight gradient reads
 // dpq): dpq rows are written as hi / mid / lo bf16 planes (dpq3, plane stride
 // ps3) instead of fp32 rows.
-template <int VEC, bool CM = false, bool TREE = false, bool PL3 = false>
+template <int VEC, bool TREE = false, bool PL3 = false>
 __global__ __launch_bounds__(256) void dq_chunk_kernel(
     const int2* __restrict__ chunks, const int* __restrict__ nchunks, const int2* __restrict__ occ2,
     const float* __restrict__ dagg, int64_t ld_dagg, const float* __restrict__ q, int hid,
-    float* __restrict__ dpq, float* __restrict__ part, const int32_t* __restrict__ q_src = nullptr,
-    int32_t* __restrict__ csrc = nullptr, const int* __restrict__ off = nullptr,
+    float* __restrict__ dpq, float* __restrict__ part, const int* __restrict__ off = nullptr,
     const int* __restrict__ cbase = nullptr, int* __restrict__ tk = nullptr, int64_t tk_stride = 0,
     uint16_t* __restrict__ dpq3 = nullptr, int64_t ps3 = 0) {
   const int lane = threadIdx.x & 63;
@@ -860,7 +856,7 @@ __global__ __launch_bounds__(256) void dq_chunk_kernel(
     dsc = chunks[wid];
     if (lane < kDqChunk) oc = occ2[wid * kDqChunk + lane];
   }
-  if (!CM && h4 <= 64 * VEC) {
+  if (h4 <= 64 * VEC) {
     // One column pass per chunk: each chunk's result is stored only after the
     // NEXT chunk's rows have been issued.  vmcnt counts stores and loads in
     // issue order, so rows loaded behind a store also waited for it: every
@@ -955,8 +951,7 @@ __global__ __launch_bounds__(256) void dq_chunk_kernel(
       if (lane < kDqChunk) oc_n = occ2[(ci + nw) * kDqChunk + lane];
     }
     const int u = dsc.x, n = dsc.y & 0xff;
-    const bool split = !CM && (dsc.y & kDqSplit) != 0;
-    if (CM && lane == 0) csrc[ci] = q_src[u];
+    const bool split = (dsc.y & kDqSplit) != 0;
     const int32_t my_row = oc.x;
     const float my_w = __int_as_float(oc.y);
     for (int c0 = 0; c0 < h4; c0 += 64 * VEC) {
@@ -1003,7 +998,7 @@ __global__ __launch_bounds__(256) void dq_chunk_kernel(
           }
         }
       }
-      float4* o = reinterpret_cast<float4*>(split || CM ? part + ci * hid : dpq + (int64_t)u * hid);
+      float4* o = reinterpret_cast<float4*>(split ? part + ci * hid : dpq + (int64_t)u * hid);
 #pragma unroll
       for (int v = 0; v < VEC; ++v) {
         const int c = c0 + v * 64 + lane;
@@ -2024,33 +2019,21 @@ int dq_tree_levels(int64_t max_chunks) {
 int launch_dq_chunks(const DqChunkParams& p, hipStream_t st) {
   PS_REQUIRE(p.hid % 4 == 0, kErrArg, "dq: hidden dim must be a multiple of 4");
   // persistent waves (each prefetches its next chunk); 512 to 4096 blocks
-  // measured alike at C2 (round 5), 1024 to 8192 at C2 and C4 (round 6), 2048
-  // kept (PINSAGE_DQ_GRID: the cap, A/B)
-  static const int grid_cap = getenv("PINSAGE_DQ_GRID") ? std::max(1, atoi(getenv("PINSAGE_DQ_GRID"))) : 2048;
-  const int grid = grid_for(p.max_chunks * 64, 256, grid_cap);
-  if (p.csrc) {  // chunk rows: masked partials in part, no combine
-    PS_REQUIRE(p.q_src, kErrArg, "dq: chunk rows need the rows' source indices");
-    if (p.hid >= 512)
-      hipLaunchKernelGGL((dq_chunk_kernel<2, true>), dim3(grid), dim3(256), 0, st, p.chunks, p.nchunks, p.occ2, p.dagg,
-                         p.ld_dagg, p.q, p.hid, p.dpq, p.part, p.q_src, p.csrc);
-    else
-      hipLaunchKernelGGL((dq_chunk_kernel<1, true>), dim3(grid), dim3(256), 0, st, p.chunks, p.nchunks, p.occ2, p.dagg,
-                         p.ld_dagg, p.q, p.hid, p.dpq, p.part, p.q_src, p.csrc);
-    PS_CHECK_LAUNCH();
-    return kOk;
-  }
+  // measured alike at C2 (round 5), 1024 to 8192 at C2 and C4 (round 6: C4
+  // 0.420-0.429 ms/step for all, C2 0.384-0.387), 2048 kept
+  const int grid = grid_for(p.max_chunks * 64, 256, 2048);
   // (an XCD-sliced form -- block b on column slice b % 8 of every chunk, so
   // each XCD gathers its eighth of d_agg from its own L2 -- was bitwise this
   // kernel and slower in the step: C2 0.398-0.406 -> 0.408-0.50 ms, C4
   // 0.426-0.431 -> 0.447-0.452, round 6; removed)
   if (p.tk && p.cbase && p.hid <= 512 && p.dpq3) {  // the same, dpq written as bf16 planes
     if (p.hid > 256)
-      hipLaunchKernelGGL((dq_chunk_kernel<2, false, true, true>), dim3(grid), dim3(256), 0, st, p.chunks, p.nchunks,
-                         p.occ2, p.dagg, p.ld_dagg, p.q, p.hid, p.dpq, p.part, nullptr, nullptr, p.off, p.cbase, p.tk,
+      hipLaunchKernelGGL((dq_chunk_kernel<2, true, true>), dim3(grid), dim3(256), 0, st, p.chunks, p.nchunks,
+                         p.occ2, p.dagg, p.ld_dagg, p.q, p.hid, p.dpq, p.part, p.off, p.cbase, p.tk,
                          p.max_chunks, p.dpq3, p.ps3);
     else
-      hipLaunchKernelGGL((dq_chunk_kernel<1, false, true, true>), dim3(grid), dim3(256), 0, st, p.chunks, p.nchunks,
-                         p.occ2, p.dagg, p.ld_dagg, p.q, p.hid, p.dpq, p.part, nullptr, nullptr, p.off, p.cbase, p.tk,
+      hipLaunchKernelGGL((dq_chunk_kernel<1, true, true>), dim3(grid), dim3(256), 0, st, p.chunks, p.nchunks,
+                         p.occ2, p.dagg, p.ld_dagg, p.q, p.hid, p.dpq, p.part, p.off, p.cbase, p.tk,
                          p.max_chunks, p.dpq3, p.ps3);
     PS_CHECK_LAUNCH();
     return kOk;
@@ -2058,12 +2041,12 @@ int launch_dq_chunks(const DqChunkParams& p, hipStream_t st) {
   PS_REQUIRE(!p.dpq3, kErrArg, "dq: planes output needs the split-row tree and hid <= 512");
   if (p.tk && p.cbase && p.hid <= 512) {  // split rows combined by their own chunks (no combine launch)
     if (p.hid > 256)
-      hipLaunchKernelGGL((dq_chunk_kernel<2, false, true>), dim3(grid), dim3(256), 0, st, p.chunks, p.nchunks, p.occ2,
-                         p.dagg, p.ld_dagg, p.q, p.hid, p.dpq, p.part, nullptr, nullptr, p.off, p.cbase, p.tk,
+      hipLaunchKernelGGL((dq_chunk_kernel<2, true>), dim3(grid), dim3(256), 0, st, p.chunks, p.nchunks, p.occ2,
+                         p.dagg, p.ld_dagg, p.q, p.hid, p.dpq, p.part, p.off, p.cbase, p.tk,
                          p.max_chunks);
     else
-      hipLaunchKernelGGL((dq_chunk_kernel<1, false, true>), dim3(grid), dim3(256), 0, st, p.chunks, p.nchunks, p.occ2,
-                         p.dagg, p.ld_dagg, p.q, p.hid, p.dpq, p.part, nullptr, nullptr, p.off, p.cbase, p.tk,
+      hipLaunchKernelGGL((dq_chunk_kernel<1, true>), dim3(grid), dim3(256), 0, st, p.chunks, p.nchunks, p.occ2,
+                         p.dagg, p.ld_dagg, p.q, p.hid, p.dpq, p.part, p.off, p.cbase, p.tk,
                          p.max_chunks);
     PS_CHECK_LAUNCH();
     return kOk;

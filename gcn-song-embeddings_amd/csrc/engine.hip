@@ -58,10 +58,8 @@ struct LayerBuf {
   // backward
   size_t dY = 0, dp = 0, dagg = 0, dpq = 0, cnt = 0, bsum = 0, off = 0, cursor = 0, cbase = 0,
          occ2 = 0, occ2b = 0, chunks = 0, nchunks = 0, dqpart = 0, split = 0, nsplit = 0;
-  size_t csrc = 0;  // chunk rows' source indices (bottom layer, Engine::dq_chunk_rows)
   int64_t max_chunks = 0, max_split = 0;
   size_t dqtk = 0;  // split-row tree tickets (dq_tree_levels x max_chunks ints, self-resetting)
-  size_t dpq3 = 0;  // (layer 0, Engine::wgrad_planes) dpq as bf16 planes [3][N.cap][hid]
   int64_t dqtk_len = 0;
   // parameter offsets (floats) into the flat param / grad buffers
   int64_t pQw = 0, pQb = 0, pWw = 0, pWb = 0;
@@ -115,23 +113,16 @@ struct Engine {
   // pass) 0.4645 -> 0.4665, 50.5 -> 75.2.  PINSAGE_FUSED_NEXT_Q=0 / 1 forces
   // it off / on wherever the 32-row form runs.
   int fused_next_q = getenv("PINSAGE_FUSED_NEXT_Q") ? atoi(getenv("PINSAGE_FUSED_NEXT_Q")) : -1;
-  // PINSAGE_DQ_CHUNK_ROWS=1: the bottom layer's Q weight gradient over dq
-  // chunk rows (masked per-chunk partials, h gathered per chunk) instead of
-  // combined dpq rows, so the combine launch leaves the chain.  Measured (one
-  // session, ms/step, bwd.layer.l0 µs): C2 0.451 -> 0.454, 167 -> 169; C4
-  // 0.483 -> 0.476, 183 -> 179 -- the GEMM's K grows by the split rows' extra
-  // chunks (C2 Q0 wgrad 69 -> 79 µs) about as much as the combine saved.
-  bool dq_chunk_rows = getenv("PINSAGE_DQ_CHUNK_ROWS") && atoi(getenv("PINSAGE_DQ_CHUNK_ROWS")) != 0;
-  // PINSAGE_CSR_FORK: the frontier's CSR transposes with a fork onto side[0]
-  // (engine_frontier): 1 = layer 0's CSR on side[0] beside the upper layers',
+  // (The bottom layer's Q weight gradient over dq chunk rows instead of
+  // combined dpq rows measured even -- C2 0.451 -> 0.454 ms/step, C4 0.483 ->
+  // 0.476: the GEMM's K grew about as much as the combine saved -- retired.)
+  // PINSAGE_CSR_FORK: the frontier's CSR transposes with a fork onto side[2]
+  // (engine_frontier): 1 = layer 0's CSR on side[2] beside the upper layers',
   // 2 = an empty branch (fork + join, no work); 0 (default) = one stream.
   // Either fork is joined back into the frontier's stream before
   // engine_frontier returns, so no engine call leaves a side stream unjoined
   // inside a caller's capture (tests/test_gpu_trainer.py)
   int csr_fork = getenv("PINSAGE_CSR_FORK") ? atoi(getenv("PINSAGE_CSR_FORK")) : 0;
-  // which side stream the frontier forks: 2 (default, its own), or 0 (the
-  // backward's side[0]: the round-5 shape, kept for tools/dbg reproduction)
-  int csr_fork_stream = getenv("PINSAGE_CSR_FORK_STREAM") ? atoi(getenv("PINSAGE_CSR_FORK_STREAM")) : 2;
   // pinsage_engine_set_frontier_fork(e, 0): the next frontiers do not fork
   // (a caller running the frontier on a branch of a graph being captured:
   // forking the engine's stream off a capture branch -- not the capture's
@@ -143,11 +134,11 @@ struct Engine {
   // split-K GEMM + reduce_slabs_2d; 1 (default) every site it supports, 0 none
   int wgrad_kw = getenv("PINSAGE_WGRAD_KW") ? atoi(getenv("PINSAGE_WGRAD_KW")) : 1;
   // the side stream's long-K weight gradients run beside the chain's kernels:
-  // PINSAGE_KW_SIDE_FORM 1 = the 64-KiB form (wgrad.hip), so a CU holding one
-  // still takes the chain's workgroups; PINSAGE_KW_SIDE_WG = their grid target
-  // (128: half the CUs, so the chain's dq / dY W launches beside them keep the
-  // rest; C4 -4 us, C4 B 4096 -23 us, C2 / C3 even against 256)
-  int kw_side_form = getenv("PINSAGE_KW_SIDE_FORM") ? atoi(getenv("PINSAGE_KW_SIDE_FORM")) : 0;
+  // PINSAGE_KW_SIDE_WG = their grid target (128: half the CUs, so the chain's
+  // dq / dY W launches beside them keep the rest; C4 -4 us, C4 B 4096 -23 us,
+  // C2 / C3 even against 256).  (A 4-wave, 2-stage form of the kernel for
+  // them, so that a CU holding one still took the chain's workgroups, measured
+  // even, and the main stream's dQ0 in it 0.391 -> 0.401 ms at C2: retired.)
   int kw_side_wg = getenv("PINSAGE_KW_SIDE_WG") ? atoi(getenv("PINSAGE_KW_SIDE_WG")) : 128;
   // PINSAGE_DQ_TREE (default 1): rows of the transposed aggregation split over
   // several chunks are summed by their chunk waves as a fixed fan-in-8 tree
@@ -155,25 +146,12 @@ struct Engine {
   // (three interleaved pairs at C2, ms/step: 0.3949 / 0.3975 / 0.3985 with the
   // combine launch, 0.3872 / 0.3855 / 0.3939 without; C4 even)
   int dq_tree = getenv("PINSAGE_DQ_TREE") ? atoi(getenv("PINSAGE_DQ_TREE")) : 1;
-  // the input feature table as hi / mid / lo bf16 planes [3][n][d_in]
-  // (pinsage_engine_set_feature_planes; null: none): the layer-0 Q weight
-  // gradient then runs on pre-split operands (wgrad_pl_kernel), the
-  // transposed aggregation writing layer 0's dpq as planes too (lb.dpq3)
-  const uint16_t* fplanes = nullptr;
-  int64_t fplanes_ps = 0;
-  // the input feature table as its interleaved split-bf16 table [n][ld >= 3
-  // d_in] (pinsage_engine_set_feature_ilv; null: none): the layer-0 Q
-  // projection then reads each gathered row's 16-k stage as one 96-B piece and
-  // converts nothing (gemm.hip a_ilv), with Q0 split per step into the
-  // workspace's table (qw_ilv) beside the W planes (fwd.wsplit)
-  const uint16_t* f_ilv = nullptr;
-  int64_t f_ilv_ld = 0;
-  // PINSAGE_WGRAD_PLANES=1: carve layer 0's dpq planes buffer so the planes
-  // form can run (default 0: measured no faster -- C2 dQ0 53.4 us fp32 8-wave
-  // form vs 54.0 us on planes, tools/wgrad_bench.py, round 6: the 12-KiB
-  // stages fit only 4 waves x 3 stages in LDS, and the 4-wave fp32 form is
-  // 63.7 us; the split the planes save is ~10 us of it)
-  int wgrad_planes = getenv("PINSAGE_WGRAD_PLANES") ? atoi(getenv("PINSAGE_WGRAD_PLANES")) : 0;
+  // (Layer 0 on pre-split copies of the feature table is retired from the
+  // engine: the Q weight gradient on bf16 planes measured C2 dQ0 54.0 us
+  // against the fp32 8-wave form's 53.4 and the step 0.410-0.417 against
+  // 0.381-0.391 ms; the Q projection on the interleaved split table Q0 62.7 ->
+  // 58.0 us but the step +8 us, Q0 being split per step.  The kernels remain
+  // as library entries: pinsage_wgrad_planes, pinsage_linear_ilv.)
   // a deque: Timed scopes nest and hold pointers to their sites, which must
   // stay valid when an inner scope appends a new site
   std::deque<TimingSite> sites;
@@ -205,7 +183,6 @@ struct Engine {
   // accumulation of repeated nodes' gradients (conv.hip det_put / rep_sum_kernel)
   size_t rank_off = 0, pos_sorted = 0, Gp = 0;
   size_t slab_main = 0, bslab_main = 0;  // split-K slabs of the main stream's weight gradient
-  size_t qw_ilv = 0;                     // Q0's interleaved split table [hid][3 d_in] (f_ilv)
   int64_t slab_floats = 0;
   // stream-K scratch of the main stream's GEMMs (gemm.h)
   size_t sk_slab = 0, sk_cnt = 0;
@@ -253,19 +230,12 @@ struct Engine {
   // then ends after the chain)
   int defer_side = getenv("PINSAGE_DEFER_SIDE") ? atoi(getenv("PINSAGE_DEFER_SIDE")) : 3;
   std::vector<std::function<int()>> pend;  // deferred side launches, in order
-  // PINSAGE_FORK_PLAN: every fork point on the chain costs the chain's next
-  // launch ~5.5 us (the rocprofv3 step timeline: the node after a fork starts
-  // late), so side launches are merged into fewer forks -- side work may
-  // always start LATER than its inputs exist.  Bit 0: the loss monitors ride
-  // on the head backward's fork instead of forking at the loss; bit 1: layer
-  // l > 0's Q weight gradient rides on the next W-gradient fork (layer l-1's,
-  // after its normalisation backward); bit 2: layer 0's W weight gradient (and
-  // what rides with it) forks with the optimizer pass, after layer 0's dcat.
-  int fork_plan = getenv("PINSAGE_FORK_PLAN") ? atoi(getenv("PINSAGE_FORK_PLAN")) : 0;
-  // launches with no fork point of their own (fork_plan bit 0: the monitors),
-  // enqueued on the side stream of the next fork, after its wait
-  std::vector<std::function<int(hipStream_t)>> ride;
-  hipStream_t ride_st = nullptr;  // the stream the riders are ordered behind
+  // (Merging side launches into fewer fork points -- the monitors on the head
+  // backward's fork, layer l's Q gradient on the next W-gradient fork, layer
+  // 0's W gradient with the optimizer pass -- trained bitwise alike and
+  // measured even or slower: C2 the first two 0.3935 / 0.3946 / 0.3858 / 0.3886
+  // against 0.3912 / 0.3921 / 0.3841 / 0.3901 ms, all three +5 us, C4 +3-7 us
+  // -- the side work then ends later.  The A/B knob is retired.)
   // the on-the-fly step (pinsage_engine_set_fly, fly.hip): the virtual nodes
   // x0 .. x0 + *fly_nx - 1 join the top set, and the loss hands each the
   // summed G row of its real node fly_xids[j] (call fly_xids[j] / fly_unit)
@@ -339,31 +309,18 @@ static int dep(Engine& E, hipStream_t from, hipStream_t to) {
 // binds to an event recorded on `from` now; with `defer` the launch itself
 // waits in E.pend until run_pend (after the main chain's next launch).
 static int fork_side(Engine& E, hipStream_t from, hipStream_t to, bool defer, std::function<int()> fn) {
-  std::vector<std::function<int(hipStream_t)>> ride;
-  if (from == E.ride_st) ride.swap(E.ride);  // (only a fork behind the riders' inputs)
-  if (from == to) {
-    for (auto& r : ride) PS_TRY(r(to));
-    return fn();
-  }
+  if (from == to) return fn();
   hipEvent_t e = E.ev[(size_t)(E.ev_next++ % kEvents)];
   PS_CHECK_HIP(hipEventRecord(e, from));
   if (!defer) {
     PS_CHECK_HIP(hipStreamWaitEvent(to, e, 0));
-    for (auto& r : ride) PS_TRY(r(to));
     return fn();
   }
-  E.pend.push_back([to, e, fn, ride]() -> int {
+  E.pend.push_back([to, e, fn]() -> int {
     PS_CHECK_HIP(hipStreamWaitEvent(to, e, 0));
-    for (auto& r : ride) PS_TRY(r(to));
     return fn();
   });
   return kOk;
-}
-// launches still riding (no fork has taken them): fork them now
-static int flush_ride(Engine& E) {
-  if (E.ride.empty()) return kOk;
-  PS_TRY(ensure_streams(E));
-  return fork_side(E, E.ride_st, E.side[0], false, []() -> int { return kOk; });
 }
 static int run_pend(Engine& E) {
   std::vector<std::function<int()>> v;
@@ -507,16 +464,13 @@ static void layout(Engine& E) {
     lb.chunks = carve(cur, lb.max_chunks * 8);
     lb.nchunks = carve(cur, 16);
     lb.dqpart = carve(cur, lb.max_chunks * c.hid * 4);  // partials of split dq rows
-    lb.csrc = carve(cur, lb.max_chunks * 4);
     lb.max_split = dq_split_capacity(FS, (int)T);
     lb.split = carve(cur, lb.max_split * 8);
     lb.nsplit = carve(cur, 16);
     lb.dqtk_len = (int64_t)dq_tree_levels(lb.max_chunks) * lb.max_chunks;
     lb.dqtk = carve(cur, lb.dqtk_len * 4);
-    if (&lb == &E.L[0] && E.wgrad_planes) lb.dpq3 = carve(cur, 3 * FN * c.hid * 2);
   }
   const int64_t top = E.L.back().S.cap;
-  E.qw_ilv = carve(cur, c.hid * 3 * E.L[0].d * 2);
   E.ids = carve(cur, c.max_pos * 8 + 16);  // + Adam coefficients staged behind the ids
   E.pos_rank = carve(cur, c.max_pos * 4);
   E.H1 = carve(cur, top * c.out * 4);
@@ -693,12 +647,13 @@ static int engine_frontier(Engine& E, void* ws, const int64_t* ids_dev, int64_t 
   PS_TRY(csr_prepare());
   // (PINSAGE_CSR_FORK) the fork's wait binds to an event recorded on st here,
   // after the index tables the CSR builds read; the join below is recorded on
-  // side[0] after its last launch and waited on st before this call returns
+  // its side stream after the last launch and waited on st before this call
+  // returns
   hipStream_t s_fk = st;
   const int csr_fork = E.frontier_fork_ok ? E.csr_fork : 0;
   if (csr_fork) {
     PS_TRY(ensure_streams(E));
-    s_fk = E.side[std::min(std::max(E.csr_fork_stream, 0), 2)];
+    s_fk = E.side[2];
     PS_TRY(dep(E, st, s_fk));
   }
   for (int l = Lc - 1; l >= 0; --l) {
@@ -727,7 +682,7 @@ static int engine_frontier(Engine& E, void* ws, const int64_t* ids_dev, int64_t 
     cb.occ2_tmp = at<int2>(ws, lb.occ2b);
     PS_TRY(launch_csr_build(cb, sl));
   }
-  if (csr_fork) PS_TRY(dep(E, s_fk, st));  // join: nothing of this call stays on side[0]
+  if (csr_fork) PS_TRY(dep(E, s_fk, st));  // join: nothing of this call stays on side[2]
   return kOk;
 }
 
@@ -756,13 +711,6 @@ static int engine_layers(Engine& E, void* ws, hipStream_t st) {
                                   st));
     }
   }
-  // Q0 on the feature table's interleaved split (f_ilv): Q0 split per step
-  const bool q0_ilv = E.f_ilv && E.L[0].d % 16 == 0;
-  if (q0_ilv) {
-    Timed ts(E, "fwd.wsplit_q", st);
-    PS_TRY(launch_split_ilv(E.params + E.L[0].pQw, E.L[0].d, c.hid, (int)E.L[0].d, at<uint16_t>(ws, E.qw_ilv),
-                            3 * E.L[0].d, st));
-  }
   int q_done = 0;  // this layer's q rows came out of the layer below's kernel (AggNextQ)
   int head_done = 0;  // the head ran inside the top layer's kernel (AggHead)
   for (int l = 0; l < Lc; ++l) {
@@ -786,12 +734,6 @@ static int engine_layers(Engine& E, void* ws, hipStream_t st) {
     q.ldc = c.hid;
     q.bias = E.params + lb.pQb;
     q.act = true;
-    if (l == 0 && q0_ilv) {
-      q.a_ilv = E.f_ilv;
-      q.lda_ilv = E.f_ilv_ld;
-      q.b_ilv = at<uint16_t>(ws, E.qw_ilv);
-      q.ldb_ilv = 3 * lb.d;
-    }
     {
       Timed tt(E, lname("fwd.q_gemm", l), st);
       with_sk(E, ws, q);
@@ -928,11 +870,6 @@ struct WGrad {
   float* dst = nullptr;
   int64_t ld_dst = 0;
   float* dst_b = nullptr;
-  // pre-split operands (wgrad.hip wgrad_pl_kernel): both set, or neither
-  const uint16_t* A3 = nullptr;
-  int64_t a3_ps = 0;
-  const uint16_t* B3 = nullptr;
-  int64_t b3_ps = 0;
 };
 
 // Adam applied by the gradient reductions (pinsage_engine_backward_adam)
@@ -991,22 +928,16 @@ static int weight_grad(Engine& E, void* ws, const WGrad& w, hipStream_t st, cons
     k.dst = w.dst;
     k.ld_dst = w.ld_dst;
     k.dst_b = w.dst_b;
-    k.A3 = w.A3;
-    k.a3_ps = w.a3_ps;
-    k.B3 = w.B3;
-    k.b3_ps = w.b3_ps;
     if (adam) k.ad = *adam;
     k.slab = slab;
     k.bslab = bslab;
     k.cnt = at<int>(ws, main ? E.kw_cnt_main : E.kw_cnt_side);
-    k.form = main ? 0 : E.kw_side_form;  // (the main stream's dQ0 in the 64-KiB form: 0.391 -> 0.401 ms at C2)
     k.S = wgrad_kw_splits(w.M, w.N, w.K_hint > 0 ? std::min(w.K_hint, w.K_max) : w.K_max,
                           main ? 256 : E.kw_side_wg);
     PS_REQUIRE((int64_t)k.S * w.M * w.N <= E.slab_floats, kErrWorkspace, "engine: wgrad slab too small");
     if (adam && after_use) PS_CHECK_HIP(hipStreamWaitEvent(st, after_use, 0));
     return launch_wgrad_kw(k, st);
   }
-  PS_REQUIRE(!w.A3 && !w.B3, kErrArg, "engine: pre-split operands need the long-K weight-gradient kernel");
   int cfg = 0, S = 1;
   // (a side-stream target of 256 workgroups measured faster at C2 and slower
   // at C4, 128 slower, and a grid cap on side launches even or slower: one
@@ -1080,18 +1011,6 @@ static int engine_backward(Engine& E, void* ws, hipStream_t st, const AdamStep* 
   // weight gradients run on s_wg, each forked once its inputs exist on st
   const bool dfr = (E.defer_side & 1) != 0;
   PS_REQUIRE(stage < 0 || !adam, kErrArg, "engine: a staged backward runs without the fused optimizer");
-  // side launches waiting for a later fork (E.fork_plan bits 1, 2): every
-  // fork_late takes them along, ahead of its own launch
-  std::vector<std::function<int()>> late;
-  auto fork_late = [&](hipStream_t to, std::function<int()> fn) -> int {
-    std::vector<std::function<int()>> v;
-    v.swap(late);
-    if (v.empty()) return fork_side(E, st, to, dfr, fn);
-    return fork_side(E, st, to, dfr, [v, fn]() -> int {
-      for (auto& f : v) PS_TRY(f());
-      return fn();
-    });
-  };
   if (stage <= 0) {
   Timed t_hb(E, "bwd.head", st);
   auto wgrad_g2 = [&]() -> int {  // dG2 = dZ^T H1 beside the chain
@@ -1141,7 +1060,7 @@ static int engine_backward(Engine& E, void* ws, hipStream_t st, const AdamStep* 
     hb.Gp = E.reps_in_gp ? at<float>(ws, E.Gp) : nullptr;
     PS_TRY(launch_head_bwd(hb, st));
     PS_TRY(run_pend(E));  // the loss monitors (PINSAGE_DEFER_SIDE bit 1)
-    PS_TRY(fork_late(s_wg, wgrad_g2));
+    PS_TRY(fork_side(E, st, s_wg, dfr, wgrad_g2));
   } else {
     GemmParams p;  // dP1 = (dZ G2) * lrelu'(H1)
     p.M_dev = cnt(top.S);
@@ -1185,7 +1104,7 @@ static int engine_backward(Engine& E, void* ws, hipStream_t st, const AdamStep* 
     w.dst = gr + E.pG1w;
     w.ld_dst = o;
     w.dst_b = gr + E.pG1b;
-    PS_TRY(fork_late(s_wg, [&E, ws, w, s_wg, st]() -> int {
+    PS_TRY(fork_side(E, st, s_wg, dfr, [&E, ws, w, s_wg, st]() -> int {
       Timed tw(E, "bwd.wgrad.g1", s_wg);
       return weight_grad(E, ws, w, s_wg, "bwd.wgrad.g1", nullptr, nullptr, false, s_wg != st);
     }));
@@ -1263,8 +1182,7 @@ static int engine_backward(Engine& E, void* ws, hipStream_t st, const AdamStep* 
         Timed tw(E, lname("bwd.w_wgrad", l), s_w);
         return weight_grad(E, ws, w_wgrad, s_w, lname("bwd.w_wgrad", l), nullptr, nullptr, false, s_w != st);
       };
-      if (l == 0 && (E.fork_plan & 4)) late.push_back(wfn);  // (forked with the optimizer pass)
-      else PS_TRY(fork_late(s_w, wfn));
+      PS_TRY(fork_side(E, st, s_w, dfr, wfn));
       Timed td(E, lname("bwd.dcat", l), st);
       PS_TRY(launch_gemm(p, st));
       E.sk_used[lname("bwd.dcat", l)] = gemm_last_stream_k();
@@ -1273,19 +1191,12 @@ static int engine_backward(Engine& E, void* ws, hipStream_t st, const AdamStep* 
     if (adam && l == 0) {  // every gradient but Q0's exists on s_w; W0 was read last
       const int64_t off = l0.pWw, n = E.n_params - l0.pWw;
       const AdamStep a = *adam;
-      PS_TRY(fork_late(s_w, [&E, s_w, off, n, a]() -> int {
+      PS_TRY(fork_side(E, st, s_w, dfr, [&E, s_w, off, n, a]() -> int {
         Timed ta(E, "adam", s_w);
         return launch_adam(E.params + off, E.grads + off, E.adam_m + off, E.adam_v + off, n, a.coef,
                            a.beta1, a.beta2, a.eps, s_w);
       }));
-    } else if (l == 0 && !late.empty()) {
-      PS_TRY(fork_late(s_w, []() -> int { return kOk; }));
     }
-    const bool chunk_rows = l == 0 && E.dq_chunk_rows;
-    // layer 0 on pre-split operands: dpq written as planes, the Q weight
-    // gradient on them and on the feature table's planes (wgrad_pl_kernel)
-    const bool planes = l == 0 && E.fplanes && lb.dpq3 && E.dq_tree && !chunk_rows && hd <= 512 && E.wgrad_kw &&
-                        wgrad_kw_supported(hd, d, -1, false) && (int64_t)(hd / 64) * (d / 64) <= E.kw_cnt_len;
     DqChunkParams dq;
     dq.chunks = at<int2>(ws, lb.chunks);
     dq.nchunks = at<int>(ws, lb.nchunks);
@@ -1301,41 +1212,29 @@ static int engine_backward(Engine& E, void* ws, hipStream_t st, const AdamStep* 
     dq.hid = hd;
     dq.dpq = at<float>(ws, lb.dpq);
     dq.part = at<float>(ws, lb.dqpart);
-    dq.q_src = at<int32_t>(ws, lb.q_src);
-    if (chunk_rows) dq.csrc = at<int32_t>(ws, lb.csrc);
     if (E.dq_tree) {
       dq.cbase = at<int>(ws, lb.cbase);
       dq.tk = at<int>(ws, lb.dqtk);
     }
-    if (planes) dq.dpq3 = at<uint16_t>(ws, lb.dpq3);
-    dq.ps3 = lb.N.cap * hd;
     PS_TRY(launch_dq_chunks(dq, st));
     PS_TRY(run_pend(E));
     WGrad q_wgrad;
     {
-      // dQ = dpq^T h[q_src], dQb = colsum(dpq); chunk rows: the same sums over
-      // the masked chunk partials, h gathered through csrc
+      // dQ = dpq^T h[q_src], dQb = colsum(dpq)
       WGrad w;
-      w.A = at<float>(ws, chunk_rows ? lb.dqpart : lb.dpq);
+      w.A = at<float>(ws, lb.dpq);
       w.lda = hd;
       w.M = hd;
       w.B = h;
       w.ldb = ldh;
-      w.b_idx = at<int32_t>(ws, chunk_rows ? lb.csrc : lb.q_src);
+      w.b_idx = at<int32_t>(ws, lb.q_src);
       w.N = d;
-      w.K_dev = chunk_rows ? at<int>(ws, lb.nchunks) : cnt(lb.N);
-      w.K_max = chunk_rows ? lb.max_chunks : lb.N.cap;
+      w.K_dev = cnt(lb.N);
+      w.K_max = lb.N.cap;
       w.K_hint = lb.N.hint;
       w.dst = gr + lb.pQw;
       w.ld_dst = d;
       w.dst_b = gr + lb.pQb;
-      if (planes) {
-        w.A3 = at<uint16_t>(ws, lb.dpq3);
-        w.a3_ps = lb.N.cap * hd;
-        w.B3 = E.fplanes;
-        w.b3_ps = E.fplanes_ps;
-        w.ldb = d;
-      }
       q_wgrad = w;
     }
     if (l > 0) {
@@ -1346,8 +1245,7 @@ static int engine_backward(Engine& E, void* ws, hipStream_t st, const AdamStep* 
         return weight_grad(E, ws, q_wgrad, s_wg, lname("bwd.q_wgrad", l), nullptr, nullptr, false,
                            s_wg != st);
       };
-      if (E.fork_plan & 2) late.push_back(qfn);  // (rides on the next W-gradient fork)
-      else PS_TRY(fork_late(s_wg, qfn));
+      PS_TRY(fork_side(E, st, s_wg, dfr, qfn));
       GemmParams p;  // dh = dpq Q  -> scatter-add into the rows of layer l-1
       p.M_dev = cnt(lb.N);
       p.M_hint = (int)lb.N.hint;
@@ -1378,8 +1276,6 @@ static int engine_backward(Engine& E, void* ws, hipStream_t st, const AdamStep* 
                          false));
     }
   }
-  if (!late.empty()) PS_TRY(fork_late(s_wg, []() -> int { return kOk; }));  // (a stage-0 call)
-  PS_TRY(flush_ride(E));
   PS_TRY(run_pend(E));
   // every gradient is written once the side streams drain into st (side[0]
   // also carries the loss monitors, pinsage_engine_loss)
@@ -1602,34 +1498,12 @@ int pinsage_engine_read_counts(const pinsage_engine* e, void* ws, int64_t* S, in
   return kOk;
 }
 
-int pinsage_engine_set_feature_ilv(pinsage_engine* e, const uint16_t* table, int64_t ld) {
-  if (!e || (table && (ld % 8 != 0 || ld < 3 * reinterpret_cast<Engine*>(e)->cfg.d_in))) {
-    set_error("engine_set_feature_ilv: bad argument (ld a multiple of 8, >= 3 d_in)");
-    return kErrArg;
-  }
-  Engine* E = reinterpret_cast<Engine*>(e);
-  E->f_ilv = table;
-  E->f_ilv_ld = table ? ld : 0;
-  return kOk;
-}
-
 int pinsage_engine_set_frontier_fork(pinsage_engine* e, int on) {
   if (!e) {
     set_error("engine_set_frontier_fork: null engine");
     return kErrArg;
   }
   reinterpret_cast<Engine*>(e)->frontier_fork_ok = on != 0;
-  return kOk;
-}
-
-int pinsage_engine_set_feature_planes(pinsage_engine* e, const uint16_t* planes, int64_t plane_stride) {
-  if (!e || (planes && plane_stride <= 0)) {
-    set_error("engine_set_feature_planes: bad argument");
-    return kErrArg;
-  }
-  Engine* E = reinterpret_cast<Engine*>(e);
-  E->fplanes = planes;
-  E->fplanes_ps = planes ? plane_stride : 0;
   return kOk;
 }
 
@@ -1690,27 +1564,23 @@ int pinsage_engine_init_workspace(pinsage_engine* e, void* ws, void* stream) {
 
 int pinsage_engine_forward(pinsage_engine* e, void* ws, const int64_t* ids, int64_t n_ids,
                            void* stream) {
-  PS_TRY(flush_ride(*reinterpret_cast<Engine*>(e)));
   PS_TRY(run_pend(*reinterpret_cast<Engine*>(e)));
   return engine_forward(*reinterpret_cast<Engine*>(e), ws, ids, n_ids, (hipStream_t)stream);
 }
 
 int pinsage_engine_forward_inference(pinsage_engine* e, void* ws, const int64_t* ids, int64_t n_ids,
                                      void* stream) {
-  PS_TRY(flush_ride(*reinterpret_cast<Engine*>(e)));
   PS_TRY(run_pend(*reinterpret_cast<Engine*>(e)));
   return engine_forward(*reinterpret_cast<Engine*>(e), ws, ids, n_ids, (hipStream_t)stream, false);
 }
 
 int pinsage_engine_frontier(pinsage_engine* e, void* ws, const int64_t* ids, int64_t n_ids,
                             void* stream) {
-  PS_TRY(flush_ride(*reinterpret_cast<Engine*>(e)));
   PS_TRY(run_pend(*reinterpret_cast<Engine*>(e)));
   return engine_frontier(*reinterpret_cast<Engine*>(e), ws, ids, n_ids, (hipStream_t)stream);
 }
 
 int pinsage_engine_forward_layers(pinsage_engine* e, void* ws, void* stream) {
-  PS_TRY(flush_ride(*reinterpret_cast<Engine*>(e)));
   PS_TRY(run_pend(*reinterpret_cast<Engine*>(e)));
   return engine_layers(*reinterpret_cast<Engine*>(e), ws, (hipStream_t)stream);
 }
@@ -1729,7 +1599,6 @@ int pinsage_engine_set_fork(pinsage_engine* e, void* ws_next, const int64_t* ids
 int pinsage_engine_gather_output(pinsage_engine* e, void* ws, int64_t n_ids, float* out,
                                  void* stream) {
   Engine* E = reinterpret_cast<Engine*>(e);
-  PS_TRY(flush_ride(*E));
   PS_TRY(run_pend(*E));
   return launch_gather_out(at<float>(ws, E->Z), (int)E->cfg.out, at<int32_t>(ws, E->pos_rank), n_ids,
                            out, (hipStream_t)stream);
@@ -1745,7 +1614,6 @@ int pinsage_engine_loss(pinsage_engine* e, void* ws, int64_t batch_size, float m
   }
   LayerBuf& top = E->L.back();
   hipStream_t st = (hipStream_t)stream;
-  PS_TRY(flush_ride(*E));  // (an earlier loss's monitors read what this one rewrites)
   {
     Timed t(*E, "loss", st);
     // (on the fly the repeated ranks are summed in the loss launch: the
@@ -1797,11 +1665,6 @@ int pinsage_engine_loss(pinsage_engine* e, void* ws, int64_t batch_size, float m
     Timed tm(*E, "loss.monitor", s);
     return launch_loss_monitor(part, nb4, varpart, out, B, scal, s);
   };
-  if (E->fork_plan & 1) {  // no fork at the loss: the head backward's fork takes them
-    E->ride.push_back(mon);
-    E->ride_st = st;
-    return kOk;
-  }
   return fork_side(*E, st, s0, (E->defer_side & 2) != 0, [mon, s0]() -> int { return mon(s0); });
 }
 
@@ -1823,7 +1686,6 @@ int pinsage_engine_set_fly(pinsage_engine* e, int64_t x0, const int* n_x, const 
 int pinsage_engine_set_output_grad(pinsage_engine* e, void* ws, const float* dout, int64_t n_ids,
                                    void* stream) {
   Engine* E = reinterpret_cast<Engine*>(e);
-  PS_TRY(flush_ride(*E));
   PS_TRY(run_pend(*E));
   LayerBuf& top = E->L.back();
   E->reps_in_gp = false;
@@ -1840,7 +1702,6 @@ int pinsage_engine_reset_backward(pinsage_engine* e, void* ws, void* stream) {
     return kErrArg;
   }
   Engine* E = reinterpret_cast<Engine*>(e);
-  PS_TRY(flush_ride(*E));
   PS_TRY(run_pend(*E));
   // the dY scatter-add targets of the layers below the top (the forward's
   // layer_prep zeroed them; a backward accumulates into them)
@@ -1875,7 +1736,6 @@ int pinsage_engine_backward_adam(pinsage_engine* e, void* ws, const float* coef,
 int pinsage_engine_adam(pinsage_engine* e, const float* coef, double beta1, double beta2, float eps,
                         void* stream) {
   Engine* E = reinterpret_cast<Engine*>(e);
-  PS_TRY(flush_ride(*E));
   PS_TRY(run_pend(*E));
   Timed t(*E, "adam", (hipStream_t)stream);
   if (!E->adam_m || !E->adam_v) {

@@ -37,7 +37,6 @@ struct KwParams {
   const uint16_t* B3 = nullptr;
   int64_t b3_ps = 0;
   int S = 0;                  // K splits (0: wgrad_kw_splits)
-  int form = 0;               // 0: 8 waves, 128-KiB ring; 1: 4 waves, 64-KiB ring
 };
 
 bool wgrad_kw_supported(int M, int N, int N1, bool has_b2);

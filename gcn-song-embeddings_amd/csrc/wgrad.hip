@@ -174,10 +174,11 @@ __device__ __forceinline__ void kw_finish(const KwParams& p, f32x16 (&acc)[2][2]
 
 // NW waves, each with an NS-stage private ring (NW * NS * 8 KiB):
 // (8, 2) two waves per SIMD, one stage in flight per wave (128 KiB); (4, 4) one
-// wave per SIMD, three stages in flight (128 KiB); (4, 2) one wave per SIMD, one
-// stage in flight (64 KiB: the side stream's form, which leaves a CU room for the
-// chain's kernels beside it -- a 152-KiB workgroup holds its CU alone).  GATHER: B rows come through the staged row
-// numbers (the identity for an ungathered segment), so no DMA branches.
+// wave per SIMD, three stages in flight (128 KiB).  (A (4, 2) form for the
+// side stream, whose smaller ring left a CU room for the chain's kernels
+// beside it, measured 62-64 us alone against 53.4 and even in the step:
+// removed.)  GATHER: B rows come through the staged row numbers (the identity
+// for an ungathered segment), so no DMA branches.
 // PROBE (timing diagnostics only, tools/wgrad_bench.py; results are wrong):
 // 1 = the DMAs without the products, 2 = the products without the DMAs,
 // 3 = 2 without the split (the LDS reads and MFMAs only), 4 = the whole k loop
@@ -636,9 +637,6 @@ int launch_wgrad_kw_probe(const KwParams& p_in, int probe, hipStream_t st) {
     PS_CHECK_LAUNCH();
     return kOk;
   }
-  // PINSAGE_KW_FORM (tests / microbenchmarks through the C-ABI): the form of a
-  // launch whose caller did not choose one
-  if (p.form == 0 && getenv("PINSAGE_KW_FORM")) p.form = atoi(getenv("PINSAGE_KW_FORM"));
   if (waves == 1) {  // PINSAGE_KW_WAVES=1: the register-ring k loop (REG), 8 waves
     if (gather) hipLaunchKernelGGL((wgrad_kw_kernel<8, 2, true, 0, true>), dim3(grid), dim3(512), 0, st, p);
     else hipLaunchKernelGGL((wgrad_kw_kernel<8, 2, false, 0, true>), dim3(grid), dim3(512), 0, st, p);
@@ -647,9 +645,6 @@ int launch_wgrad_kw_probe(const KwParams& p_in, int probe, hipStream_t st) {
     else if (probe == 2) hipLaunchKernelGGL((wgrad_kw_kernel<8, 2, true, 2>), dim3(grid), dim3(512), 0, st, p);
     else if (probe == 3) hipLaunchKernelGGL((wgrad_kw_kernel<8, 2, true, 3>), dim3(grid), dim3(512), 0, st, p);
     else hipLaunchKernelGGL((wgrad_kw_kernel<8, 2, true, 4>), dim3(grid), dim3(512), 0, st, p);
-  } else if (p.form == 1) {  // 4 waves x 2 stages: 64-KiB ring
-    if (gather) hipLaunchKernelGGL((wgrad_kw_kernel<4, 2, true>), dim3(grid), dim3(256), 0, st, p);
-    else hipLaunchKernelGGL((wgrad_kw_kernel<4, 2, false>), dim3(grid), dim3(256), 0, st, p);
   } else if (waves == 4) {
     if (gather) hipLaunchKernelGGL((wgrad_kw_kernel<4, 4, true>), dim3(grid), dim3(256), 0, st, p);
     else hipLaunchKernelGGL((wgrad_kw_kernel<4, 4, false>), dim3(grid), dim3(256), 0, st, p);

@@ -853,29 +853,11 @@ int pinsage_engine_offsets(const pinsage_engine* e, pinsage_engine_offsets_t* ou
 int pinsage_engine_set_tensors(pinsage_engine* e, const float* feats, int64_t ld_feats,
                                const int32_t* nb_table, const float* w_table, int64_t ld_table,
                                float* params, float* grads, float* adam_m, float* adam_v);
-/* The input feature table's hi / mid / lo bf16 planes [3][n][d_in] (from
- * pinsage_split_planes(feats, n, d_in, ld_feats, planes); plane stride in
- * elements), or null: with them the layer-0 Q weight gradient
- * (pinsage_model.py:201's AddmmBackward) runs on pre-split operands -- the
- * transposed aggregation writes layer 0's dpq as planes too -- and does no
- * conversions; the result's weights are those of the fp32 form's 4-wave
- * launch.  The caller keeps the planes equal to the split of the features the
- * engine reads (pinsage_model.Runner.bind re-splits when the tensor's version
- * changes). */
-int pinsage_engine_set_feature_planes(pinsage_engine* e, const uint16_t* planes, int64_t plane_stride);
 /* on = 0: the engine's next pinsage_engine_frontier calls do not fork its
  * side stream (PINSAGE_CSR_FORK), e.g. while the caller captures them on a
  * branch of a graph (forking off a capture branch, not the capture's origin,
  * sent hipStreamEndCapture into unbounded recursion); 1 (default) restores. */
 int pinsage_engine_set_frontier_fork(pinsage_engine* e, int on);
-/* The input feature table's interleaved split-bf16 table [n][ld] (from
- * pinsage_split_ilv(feats, ld_feats, n, d_in, table, ld); ld % 8 == 0, ld >=
- * 3 d_in), or null: with it the layer-0 Q projection (pinsage_model.py:201)
- * reads each gathered row's 16-k stage as one 96-B piece and converts nothing
- * (Q0 is split per step into the workspace); bitwise the in-register split on
- * the same 128 x 128 tiles.  The caller keeps the table equal to the split of
- * the features the engine reads. */
-int pinsage_engine_set_feature_ilv(pinsage_engine* e, const uint16_t* table, int64_t ld);
 /* Zero the workspace regions the step kernels keep zero after use (loss
  * scatter targets, CSR counters).  Call once per new workspace, before its
  * first forward. */
