@@ -19,7 +19,14 @@ selection kernel under a Jaccard key.  With it, ``Random`` (baselines.py:
 177-215) and ``compute_results_table`` (eval.py:413-443) the reference's main
 results table is produced from this package.
 
-The reference's other baseline recommenders (node2vec, implicit ALS,
+``ColTrackCF`` / ``TrackTrackCF`` (baselines.py:458-514) factorise the
+collection-track and the track-track matrix by implicit-feedback ALS.  The
+reference takes the fit from the ``implicit`` package; here ``ALS`` is this
+package's own (csrc/als.hip: a Gram kernel and a conjugate-gradient
+half-iteration), defined in its docstring, and ``similar_items`` is the cosine
+kNN above.
+
+The reference's other baseline recommenders (node2vec, implicit's lmf and bpr,
 networkx similarities, lib/gnns) are out of scope; their libraries are not
 part of this build.  Names, signatures, return types and RNG consumption
 follow the reference; compute runs in HIP (no CPU fallback).
@@ -556,6 +563,34 @@ class PersPageRank(PredictionModel):
         return psm.sample_neighborhood_topt(self.g, None, nodeset, self.n_hops, self.alpha, k)
 
 
+def _csr_ptr(rows, n_rows):
+    ptr = torch.zeros(n_rows + 1, dtype=torch.int64, device=rows.device)
+    torch.cumsum(torch.bincount(rows, minlength=n_rows), 0, out=ptr[1:])
+    return ptr
+
+
+def _membership_pairs(g, n_tracks, dev, who):
+    """(track, collection - n_tracks) of every stored edge of g with exactly one
+    track endpoint, int64 on dev, duplicates kept: nodes [0, n_tracks) are
+    tracks, the rest collections.  An edge between two tracks is dropped, one
+    between two collections raises ValueError."""
+    n_cols = len(g) - n_tracks
+    if n_tracks < 1 or n_cols < 0:
+        raise ValueError(f"{who}: {n_tracks} tracks in a graph of {len(g)} nodes")
+    dev = torch.device(dev)
+    if dev.type == "cpu":  # leaves g's device mirror alone
+        indptr, indices = torch.as_tensor(g.indptr), torch.as_tensor(g.indices)
+    else:
+        indptr, indices = g.device_csr(dev)
+    src = torch.repeat_interleave(torch.arange(len(g), dtype=torch.int64, device=dev), indptr[1:] - indptr[:-1])
+    dst = indices.to(torch.int64)
+    s_tr, d_tr = src < n_tracks, dst < n_tracks
+    if bool((~s_tr & ~d_tr).any()):
+        raise ValueError(f"{who}: an edge joins two collections")
+    keep = s_tr ^ d_tr
+    return torch.where(s_tr, src, dst)[keep], torch.where(s_tr, dst, src)[keep] - n_tracks
+
+
 class JaccardFast(PredictionModel):
     """Nearest neighbours by the Jaccard similarity of the tracks' collection
     sets (baselines.py:194-220):  |C(q) & C(t)| / (|C(q) | C(t)| + 1e-10).
@@ -590,18 +625,7 @@ class JaccardFast(PredictionModel):
         self.ids = ids
         self.n = n_tracks = len(ids)
         self.n_cols = n_cols = len(g) - n_tracks
-        if n_tracks < 1 or n_cols < 0:
-            raise ValueError(f"JaccardFast: {n_tracks} tracks in a graph of {len(g)} nodes")
-        dev = nat.device()
-        indptr, indices = g.device_csr(dev)
-        src = torch.repeat_interleave(torch.arange(len(g), dtype=torch.int64, device=dev), indptr[1:] - indptr[:-1])
-        dst = indices.to(torch.int64)
-        s_tr, d_tr = src < n_tracks, dst < n_tracks
-        if bool((~s_tr & ~d_tr).any()):
-            raise ValueError("JaccardFast: an edge joins two collections")
-        keep = s_tr ^ d_tr
-        track = torch.where(s_tr, src, dst)[keep]
-        col = torch.where(s_tr, dst, src)[keep] - n_tracks
+        track, col = _membership_pairs(g, n_tracks, nat.device(), "JaccardFast")
         # one 64-bit key per membership: unique() removes duplicates and sorts the rows
         tc = torch.unique(track * max(n_cols, 1) + col)
         ct = torch.unique(col * n_tracks + track)
@@ -611,9 +635,7 @@ class JaccardFast(PredictionModel):
 
     @staticmethod
     def _csr(rows, cols, n_rows):
-        ptr = torch.zeros(n_rows + 1, dtype=torch.int64, device=rows.device)
-        torch.cumsum(torch.bincount(rows, minlength=n_rows), 0, out=ptr[1:])
-        return ptr, cols.to(torch.int32).contiguous()
+        return _csr_ptr(rows, n_rows), cols.to(torch.int32).contiguous()
 
     def _queries(self, nodeset):
         qs = torch.as_tensor(nodeset).reshape(-1).to(torch.int64)
@@ -659,6 +681,214 @@ class JaccardFast(PredictionModel):
             if int(err):
                 raise IndexError(f"JaccardFast: query ids out of range for {n} tracks")
         return w[:, 1:].to(out_dev), nb[:, 1:].to(out_dev)
+
+
+# ----------------------------------------------------------------------------- implicit-feedback ALS
+# baselines.py:400-426 and :458-514.  A sparse matrix is the tuple
+# (ptr int64 [n_rows + 1], idx int32, val float32, n_rows, n_cols), rows with
+# ascending column ids and no cell twice, on the GPU unless ``device`` says
+# otherwise (the builders and als_loss are plain torch and run anywhere).
+ALS_MAX_FACTORS = 128  # kAlsMaxF (csrc/als.hip)
+
+
+def to_col_track_matrix(g, ids, device=None):
+    """baselines.py:402-413: collections x tracks, 1 where the collection holds
+    the track.  Membership is JaccardFast.train's rule (the reference's set
+    successors | predecessors per collection): every edge with exactly one track
+    endpoint, whichever way it points and however often it is stored; an edge
+    between two tracks is ignored, one between two collections raises ValueError."""
+    n_tracks = len(ids)
+    n_cols = len(g) - n_tracks
+    dev = nat.device() if device is None else torch.device(device)
+    track, col = _membership_pairs(g, n_tracks, dev, "to_col_track_matrix")
+    ct = torch.unique(col * n_tracks + track)
+    idx = (ct % n_tracks).to(torch.int32).contiguous()
+    return (_csr_ptr(ct // n_tracks, n_cols), idx, torch.ones(idx.numel(), dtype=torch.float32, device=dev),
+            n_cols, n_tracks)
+
+
+def to_track_track_matrix(ids, positives, device=None):
+    """baselines.py:415-426: n x n, cell (a, b) = how often the row (a, b) occurs
+    in ``positives`` ([m, 2] ids).  Not symmetrised, as in the reference; a == b
+    is a cell like any other.  An id outside [0, len(ids)) raises IndexError."""
+    n = len(ids)
+    dev = nat.device() if device is None else torch.device(device)
+    tp = _pairs(positives).to(dev)
+    if n < 1:
+        raise ValueError("to_track_track_matrix: no tracks")
+    if tp.numel() and (int(tp.min()) < 0 or int(tp.max()) >= n):
+        raise IndexError(f"to_track_track_matrix: ids out of range for {n} tracks")
+    key, counts = torch.unique(tp[:, 0] * n + tp[:, 1], return_counts=True)
+    return (_csr_ptr(key // n, n), (key % n).to(torch.int32).contiguous(), counts.to(torch.float32), n, n)
+
+
+def _csr_rows(ptr):
+    n = int(ptr.numel()) - 1
+    return torch.repeat_interleave(torch.arange(n, dtype=torch.int64, device=ptr.device), ptr[1:] - ptr[:-1])
+
+
+def als_loss(user_items, user_factors, item_factors, regularization, alpha=1.0):
+    """The ALS objective  sum_observed c (1 - x.y)^2 + sum_unobserved (x.y)^2 +
+    reg (|X|^2 + |Y|^2),  c = alpha r,  in float64 on the factors' device without
+    the dense n_users x n_items matrix:  the sum of (x.y)^2 over ALL cells is
+    sum((X^T X) * (Y^T Y)), and the observed cells replace their term."""
+    ptr, idx, val = user_items[:3]
+    X, Y = user_factors.to(torch.float64), item_factors.to(torch.float64)
+    ptr, idx, val = ptr.to(X.device), idx.to(X.device), val.to(X.device)
+    total = ((X.T @ X) * (Y.T @ Y)).sum()
+    rows = _csr_rows(ptr)
+    for i in range(0, int(idx.numel()), 1 << 20):
+        s = (X[rows[i:i + (1 << 20)]] * Y[idx[i:i + (1 << 20)].to(torch.int64)]).sum(1)
+        c = float(alpha) * val[i:i + (1 << 20)].to(torch.float64)
+        total = total + (c * (1 - s) ** 2 - s * s).sum()
+    return float(total + float(regularization) * ((X * X).sum() + (Y * Y).sum()))
+
+
+class ALS:
+    """Implicit-feedback alternating least squares (Hu, Koren, Volinsky) with the
+    conjugate-gradient row solve of Takacs et al., on the kernels of
+    csrc/als.hip: what the reference takes from
+    implicit.cpu.als.AlternatingLeastSquares (baselines.py:474, :503).  The
+    arithmetic is THIS PROJECT'S DEFINITION; that package cannot be run here and
+    no parity with its numbers is claimed.
+
+    R [n_users, n_items] has values r > 0; the confidence of an observed cell is
+    c = alpha r (used directly: its extra weight is c - 1), the preference 1.
+    One iteration solves every user row from the item factors Y, then every
+    item row from the new user factors X (R^T as the CSR).  A half-iteration
+    forms G = Y^T Y + reg I once and runs, per row u over its items i,
+
+        x = X[u];  r = -G x + sum_i (c - (c - 1)(y_i . x)) y_i;  p = r;  rs = r . r
+        if rs < 1e-20: X[u] stays
+        repeat cg_steps times:
+            Ap = G p + sum_i (c - 1)(y_i . p) y_i
+            a = rs / (p . Ap);  x += a p;  r -= a Ap;  rn = r . r
+            if rn < 1e-20: break
+            p = r + (rn / rs) p;  rs = rn
+        X[u] = x
+
+    in fp32.  Rows are independent (Jacobi) and the result depends on the inputs
+    only.  A row without items follows the same recurrence (CG drives it towards
+    0).  Initial factors: (torch.rand(n, f) - 0.5) / f on the host, users first,
+    then items, from a torch.Generator seeded with ``random_state`` or, with
+    None, from torch's global generator."""
+
+    def __init__(self, factors=128, regularization=0.01, alpha=1.0, iterations=15, cg_steps=3, random_state=None):
+        if not (4 <= int(factors) <= ALS_MAX_FACTORS and int(factors) % 4 == 0):
+            raise ValueError(f"ALS: factors = {factors}: need a multiple of 4 in [4, {ALS_MAX_FACTORS}]")
+        if not (regularization > 0 and alpha > 0 and int(iterations) >= 0 and int(cg_steps) >= 0):
+            raise ValueError("ALS: need regularization > 0, alpha > 0, iterations >= 0, cg_steps >= 0")
+        self.factors, self.regularization, self.alpha = int(factors), float(regularization), float(alpha)
+        self.iterations, self.cg_steps, self.random_state = int(iterations), int(cg_steps), random_state
+        self.user_factors = self.item_factors = None
+
+    def _table(self, given, n, gen):
+        f = self.factors
+        if given is None:
+            return ((torch.rand(n, f, generator=gen) - 0.5) / f).to("cuda")
+        t = torch.as_tensor(given)
+        if tuple(t.shape) != (n, f):
+            raise ValueError(f"ALS: factors of shape {tuple(t.shape)}, expected {(n, f)}")
+        return t.to(device="cuda", dtype=torch.float32, copy=True).contiguous()
+
+    def _half(self, csr, Y, X, G, err):
+        ptr, idx, val, n_rows, n_other = csr
+        L, f = nat.lib(), self.factors
+        nat.check(L.pinsage_als_gram(nat.ptr(Y), n_other, f, f, self.regularization, nat.ptr(G), nat.stream_ptr()),
+                  "als_gram")
+        nat.check(L.pinsage_als_half(nat.ptr(ptr), nat.ptr(idx), nat.ptr(val), n_rows, nat.ptr(Y), n_other, f,
+                                     nat.ptr(X), f, f, nat.ptr(G), self.alpha, self.cg_steps, nat.ptr(err),
+                                     nat.stream_ptr()), "als_half")
+
+    def fit(self, user_items, user_factors=None, item_factors=None):
+        """user_items: the (ptr, idx, val, n_users, n_items) CSR; the transpose is
+        built here.  Values are checked once on the host to be finite and > 0
+        (ValueError); a column id outside [0, n_items) raises IndexError.  Given
+        factor tables are copied, not written."""
+        nat.require_gpu()
+        ptr, idx, val, n_users, n_items = user_items
+        n_users, n_items = int(n_users), int(n_items)
+        if n_users < 1 or n_items < 1:
+            raise ValueError(f"ALS: a {n_users} x {n_items} matrix")
+        ptr = torch.as_tensor(ptr).to(device="cuda", dtype=torch.int64).contiguous()
+        idx = torch.as_tensor(idx).to(device="cuda", dtype=torch.int32).contiguous()
+        val = torch.as_tensor(val).to(device="cuda", dtype=torch.float32).contiguous()
+        if int(ptr.numel()) != n_users + 1 or int(idx.numel()) != int(val.numel()):
+            raise ValueError("ALS: the CSR arrays do not fit together")
+        if not bool((torch.isfinite(val) & (val > 0)).all()):
+            raise ValueError("ALS: values must be finite and > 0")
+        # R^T: a stable sort by column keeps the rows ascending within a column;
+        # an id out of range is clamped here and reported by the kernel below
+        rows = _csr_rows(ptr)
+        col = idx.to(torch.int64).clamp(0, n_items - 1)
+        order = torch.sort(col, stable=True).indices
+        csr_u = (ptr, idx, val, n_users, n_items)
+        csr_i = (_csr_ptr(col, n_items), rows[order].to(torch.int32).contiguous(), val[order].contiguous(),
+                 n_items, n_users)
+        gen = None if self.random_state is None else torch.Generator().manual_seed(int(self.random_state))
+        X = self._table(user_factors, n_users, gen)
+        Y = self._table(item_factors, n_items, gen)
+        G = torch.empty((self.factors, self.factors), dtype=torch.float32, device="cuda")
+        err = torch.zeros(1, dtype=torch.int32, device="cuda")
+        for it in range(self.iterations):
+            self._half(csr_u, Y, X, G, err)
+            if it == 0 and int(err):
+                raise IndexError(f"ALS: item ids out of range for {n_items} items")
+            self._half(csr_i, X, Y, G, err)
+        self._user_items = csr_u
+        self.user_factors, self.item_factors = X, Y
+        return self
+
+    def similar_items(self, ids, N=10):
+        """(ids int64 [nq, N], scores float32 [nq, N]): the N items nearest to each
+        of ``ids`` by cosine similarity of the item factors, best first (the
+        query itself comes first unless another item ties it), on the GPU."""
+        w, nb = _knn_cosine(self.item_factors, ids, int(N))
+        return nb, w
+
+    def loss(self):
+        """als_loss of the fitted factors (a Python float; monitoring and tests)."""
+        return als_loss(self._user_items, self.user_factors, self.item_factors, self.regularization, self.alpha)
+
+
+class _CfALS(PredictionModel):
+    def __init__(self, algo="als", factors=128):
+        if algo != "als":  # the reference's "lmf" and "bpr" come from implicit too
+            raise NotImplementedError(f"algo = {algo!r}: ALS ('als') is the only algorithm of this package")
+        self.algo = algo
+        self.factors = factors
+
+    def _fit(self, mat):
+        self.model = ALS(factors=self.factors)
+        self.model.fit(mat)
+
+    def knn(self, nodeset, k):
+        """(scores float32 [nq, k], ids int64 [nq, k]) on nodeset's device:
+        similar_items(nodeset, k + 1) with column 0 dropped, the tensors of
+        knn_from_emb(self.model.item_factors, nodeset, k)."""
+        out_dev = torch.as_tensor(nodeset).device
+        topn_nodes, topn_scores = self.model.similar_items(nodeset, N=int(k) + 1)
+        return topn_scores[:, 1:].to(out_dev), topn_nodes[:, 1:].to(out_dev)
+
+
+class TrackTrackCF(_CfALS):
+    """Matrix factorisation of the track-track co-occurrence matrix of the
+    training positives (baselines.py:458-487), by ALS."""
+
+    def train(self, g, ids, train_set, test_set, features):
+        self.ids = ids
+        self.n = len(ids)
+        self._fit(to_track_track_matrix(ids, train_set))
+
+
+class ColTrackCF(_CfALS):
+    """Matrix factorisation of the collection-track membership matrix
+    (baselines.py:489-514), by ALS."""
+
+    def train(self, g, ids, train_set, test_set, features):
+        self.ids = ids
+        self.n = len(ids)
+        self._fit(to_col_track_matrix(g, ids))
 
 
 class Random(PredictionModel):
@@ -729,4 +959,5 @@ __all__ = ["PRECOMP_K", "PredictionModel", "EmbeddingModel", "cosine_sim_ab", "k
            "low_degree_accuracy_from_ranks", "LIST_OVERLAP_MAX_K", "intra_diversity", "inter_diversity",
            "coverage", "average_degree", "degree_dist", "beyond_accuracy", "compute_beyond_accuracy_table",
            "JaccardFast", "Random", "low_co_accuracy", "low_co_accuracy_from_ranks", "LazyKnnDict",
-           "compute_results_table"]
+           "compute_results_table", "ALS_MAX_FACTORS", "ALS", "als_loss", "to_col_track_matrix",
+           "to_track_track_matrix", "ColTrackCF", "TrackTrackCF"]

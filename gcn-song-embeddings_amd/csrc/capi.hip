@@ -9,6 +9,7 @@
 
 #include "../../include/pinsage_hip.h"
 #include "aggw.h"
+#include "als.h"
 #include "capi.h"
 #include "conv.h"
 #include "cooc.h"
@@ -753,6 +754,21 @@ int pinsage_cooc_jaccard(const int64_t* t2c_ptr, const int32_t* t2c_idx, const i
                          int* err, void* stream) {
   return launch_cooc_jaccard(t2c_ptr, t2c_idx, c2t_ptr, c2t_idx, n_tracks, n_cols, queries, nq, k, scratch,
                              scratch_bytes, out_w, out_n, err, (hipStream_t)stream);
+}
+
+int64_t pinsage_als_rows_per_block(void) { return als_rows_per_block(); }
+
+int64_t pinsage_als_long_row(void) { return als_long_row(); }
+
+int pinsage_als_gram(const float* Y, int64_t n, int64_t f, int64_t ld, float reg, float* G, void* stream) {
+  return launch_als_gram(Y, n, f, ld, reg, G, (hipStream_t)stream);
+}
+
+int pinsage_als_half(const int64_t* ptr, const int32_t* idx, const float* val, int64_t n_rows, const float* Y,
+                     int64_t n_other, int64_t ldy, float* X, int64_t ldx, int64_t f, const float* G, float alpha,
+                     int64_t cg_steps, int* err, void* stream) {
+  return launch_als_half(ptr, idx, val, n_rows, Y, n_other, ldy, X, ldx, f, G, alpha, cg_steps, err,
+                         (hipStream_t)stream);
 }
 
 int64_t pinsage_knn_scratch_bytes(int64_t n, int64_t batch_rows) {

@@ -806,6 +806,53 @@ int pinsage_cooc_jaccard(const int64_t* t2c_ptr, const int32_t* t2c_idx, const i
                          int64_t nq, int64_t k, void* scratch, int64_t scratch_bytes, float* out_w, int64_t* out_n,
                          int* err, void* stream);
 
+/* ------------------------------------------------------------------ implicit-feedback ALS
+ * The fit behind ColTrackCfALS / TrackTrackCfALS (baselines.py:458-514), which
+ * the reference takes from implicit.cpu.als.AlternatingLeastSquares: the model
+ * of Hu, Koren and Volinsky solved row by row with the conjugate-gradient scheme
+ * of Takacs et al.  The arithmetic below is this project's definition; parity
+ * with that package's numbers is not claimed.
+ *
+ * pinsage_als_gram: G f32 [f][f] = Y^T Y + reg I for Y f32 [n][ld].  Fixed
+ * summation order, no float atomics: the same bits on every run, symmetric bit
+ * for bit, exact on small integers.
+ *
+ * pinsage_als_half: one half-iteration, rows X f32 [n_rows][ldx] solved in
+ * place from fixed Y f32 [n_other][ldy] and G = pinsage_als_gram(Y).  The sparse
+ * matrix is a CSR: ptr int64 [n_rows + 1], idx int32 (ids in [0, n_other)), val
+ * f32 (> 0).  With c = alpha val the confidence, for each row u over its items i:
+ *   x = X[u];  r = -G x + sum_i (c - (c - 1)(y_i . x)) y_i;  p = r;  rs = r . r
+ *   if rs < 1e-20: X[u] stays as it is
+ *   repeat cg_steps times:
+ *     Ap = G p + sum_i (c - 1)(y_i . p) y_i
+ *     a = rs / (p . Ap);  x += a p;  r -= a Ap;  rn = r . r
+ *     if rn < 1e-20: break
+ *     p = r + (rn / rs) p;  rs = rn
+ *   X[u] = x
+ * in fp32.  A row without items follows the same recurrence.  Row u reads X[u]
+ * and Y only; only columns [0, f) of X are written (padding keeps its bits);
+ * cg_steps == 0 launches nothing.  A row of at most pinsage_als_long_row() items
+ * is solved by one wave, its item sums in CSR order; a longer one by a whole
+ * workgroup, wave w summing the 64-item groups w, w + 8, ... in order and the 8
+ * partial sums added in wave order.  The form depends on the row's length
+ * alone: the output bits depend on the inputs only, not on the grid or the run.
+ * Row r belongs to the block of rows r / pinsage_als_rows_per_block(); a
+ * workgroup takes four consecutive blocks.
+ *
+ * All pointers are device memory.  err (nullable): a device int set to 1 when an
+ * id is outside [0, n_other); the id is clamped so that no access strays, and the
+ * caller raises.  A refused call (PINSAGE_ERR_ARG: f outside [4, 128] or
+ * f % 4 != 0; a leading dimension below f or not a multiple of 4; Y, X or G
+ * not 16-byte aligned or null; reg <= 0; alpha <= 0 or not finite;
+ * cg_steps < 0; a count above INT32_MAX; n_other < 1) returns before any launch
+ * and leaves X and G untouched. */
+int64_t pinsage_als_rows_per_block(void);
+int64_t pinsage_als_long_row(void);
+int pinsage_als_gram(const float* Y, int64_t n, int64_t f, int64_t ld, float reg, float* G, void* stream);
+int pinsage_als_half(const int64_t* ptr, const int32_t* idx, const float* val, int64_t n_rows, const float* Y,
+                     int64_t n_other, int64_t ldy, float* X, int64_t ldx, int64_t f, const float* G, float alpha,
+                     int64_t cg_steps, int* err, void* stream);
+
 /* ------------------------------------------------------------------ train-step engine
  * PinSageModel.forward / PinSage.train_batch (pinsage_model.py:246-265,
  * pinsage_training.py:181-214) with device-resident sizes.  Parameters live in
