@@ -187,6 +187,11 @@ _SIGS = {
     "pinsage_als_long_row": (i64, []),
     "pinsage_als_gram": (ctypes.c_int, [vp, i64, i64, i64, f32, vp, vp]),
     "pinsage_als_half": (ctypes.c_int, [vp, vp, vp, i64, vp, i64, i64, vp, i64, i64, vp, f32, i64, vp, vp]),
+    "pinsage_lmf_row_block": (i64, []),
+    "pinsage_lmf_long_row": (i64, []),
+    "pinsage_lmf_dense": (ctypes.c_int, [vp, vp, i64, i64, vp, vp, i64, i64, i64, vp, i64, vp, vp]),
+    "pinsage_lmf_update": (ctypes.c_int, [vp, vp, vp, i64, vp, vp, i64, i64, vp, vp, i64, i64, vp, i64, vp, vp, i64,
+                                          vp, f32, f32, f32, vp, vp]),
     "pinsage_engine_create": (ctypes.c_int, [ctypes.POINTER(EngineConfig), ctypes.POINTER(vp)]),
     "pinsage_engine_destroy": (None, [vp]),
     "pinsage_engine_live_count": (i64, []),

@@ -24,9 +24,13 @@ collection-track and the track-track matrix by implicit-feedback ALS.  The
 reference takes the fit from the ``implicit`` package; here ``ALS`` is this
 package's own (csrc/als.hip: a Gram kernel and a conjugate-gradient
 half-iteration), defined in its docstring, and ``similar_items`` is the cosine
-kNN above.
+kNN above.  ``ColTrackLMF`` / ``TrackTrackLMF`` are the same two classes with
+the fit the reference selects by algo="lmf": ``LMF``, logistic matrix
+factorisation by full-gradient AdaGrad ascent (csrc/lmf.hip: a fused
+sigmoid(X Y^T) Y MFMA kernel and a sparse update), again this package's own
+definition.
 
-The reference's other baseline recommenders (node2vec, implicit's lmf and bpr,
+The reference's other baseline recommenders (node2vec, implicit's bpr,
 networkx similarities, lib/gnns) are out of scope; their libraries are not
 part of this build.  Names, signatures, return types and RNG consumption
 follow the reference; compute runs in HIP (no CPU fallback).
@@ -851,16 +855,178 @@ class ALS:
         return als_loss(self._user_items, self.user_factors, self.item_factors, self.regularization, self.alpha)
 
 
-class _CfALS(PredictionModel):
-    def __init__(self, algo="als", factors=128):
-        if algo != "als":  # the reference's "lmf" and "bpr" come from implicit too
-            raise NotImplementedError(f"algo = {algo!r}: ALS ('als') is the only algorithm of this package")
-        self.algo = algo
-        self.factors = factors
+LMF_MAX_FACTORS = 128  # kLmfMaxF (csrc/lmf.hip)
+_LMF_CELLS = 1 << 24  # dense cells of lmf_objective formed at once
 
-    def _fit(self, mat):
-        self.model = ALS(factors=self.factors)
-        self.model.fit(mat)
+
+def _softplus64(s):
+    return torch.clamp(s, min=0) + torch.log1p(torch.exp(-s.abs()))
+
+
+def lmf_objective(user_items, user_factors, item_factors, user_bias, item_bias, regularization, alpha=1.0):
+    """The LMF objective (to be maximised)
+
+        L = sum_observed c s - sum_observed (1 + c) softplus(s) - sum_unobserved softplus(s)
+            - (reg / 2)(|X|^2 + |Y|^2),     s = x.y + bx + by,  c = alpha r,
+
+    in float64 on the factors' device.  The softplus sum over ALL cells runs in
+    row chunks of at most 2^24 cells; an observed cell then adds c s - c softplus(s)."""
+    ptr, idx, val = user_items[:3]
+    X, Y = user_factors.to(torch.float64), item_factors.to(torch.float64)
+    bx = torch.as_tensor(user_bias).to(device=X.device, dtype=torch.float64)
+    by = torch.as_tensor(item_bias).to(device=X.device, dtype=torch.float64)
+    ptr, idx, val = ptr.to(X.device), idx.to(X.device), val.to(X.device)
+    n_items = int(Y.shape[0])
+    step = max(1, _LMF_CELLS // max(1, n_items))
+    total = torch.zeros((), dtype=torch.float64, device=X.device)
+    for r0 in range(0, int(X.shape[0]), step):
+        s = X[r0:r0 + step] @ Y.T + bx[r0:r0 + step, None] + by[None, :]
+        total = total - _softplus64(s).sum()
+    rows = _csr_rows(ptr)
+    for i in range(0, int(idx.numel()), 1 << 20):
+        r, j = rows[i:i + (1 << 20)], idx[i:i + (1 << 20)].to(torch.int64)
+        s = (X[r] * Y[j]).sum(1) + bx[r] + by[j]
+        c = float(alpha) * val[i:i + (1 << 20)].to(torch.float64)
+        total = total + (c * (s - _softplus64(s))).sum()
+    return float(total - 0.5 * float(regularization) * ((X * X).sum() + (Y * Y).sum()))
+
+
+class LMF:
+    """Logistic matrix factorisation (Johnson, "Logistic Matrix Factorization for
+    Implicit Feedback Data", 2014) on the kernels of csrc/lmf.hip: what the
+    reference takes from implicit's LogisticMatrixFactorization with
+    algo="lmf".  The arithmetic is THIS PROJECT'S DEFINITION, the paper's
+    full-gradient AdaGrad ascent without that package's negative sampling; the
+    package cannot be run here and no parity with its numbers is claimed.
+
+    R [n_users, n_items] has values r > 0 and c = alpha r.  Tables X [n_users, f],
+    Y [n_items, f], biases bx, by; the score is s_ui = x_u . y_i + bx_u + by_i.
+    The objective to MAXIMISE is
+
+        L = sum_observed c s - sum_observed (1 + c) softplus(s) - sum_unobserved softplus(s)
+            - (reg / 2)(|X|^2 + |Y|^2)            (biases are not regularised)
+
+    One iteration updates every user row from (Y, by), then every item row from
+    the new (X, bx) with R^T as the CSR.  A half-iteration is Jacobi: every row
+    reads the old tables only.  Per row u, in fp32:
+
+        D    = sum_all i sig(s_ui) y_i          dsum = sum_all i sig(s_ui)
+        w_i  = c_ui sig(-s_ui)  for observed i        (= c (1 - sig(s)), no cancellation)
+        g    = sum_obs w_i y_i - D - reg x_u    gb = sum_obs w_i - dsum
+        h   += g^2 (elementwise)                hb += gb^2     (AdaGrad, start at 0)
+        x_u += lr g / sqrt(1e-6 + h)            bx_u += lr gb / sqrt(1e-6 + hb)
+
+    sig is evaluated stably (1 / (1 + e^-s) for s >= 0, e^s / (1 + e^s) otherwise).
+    The dense terms D, dsum come from one fused MFMA kernel (pinsage_lmf_dense:
+    no n_users x n_items buffer), the rest from pinsage_lmf_update.  The result
+    depends on the inputs only.  Initial factors: (torch.rand(n, f) - 0.5) / f on
+    the host, users first, then items, from a torch.Generator seeded with
+    ``random_state`` or, with None, from torch's global generator; biases and
+    accumulators start at zero."""
+
+    def __init__(self, factors=128, learning_rate=0.1, regularization=0.6, alpha=1.0, iterations=30,
+                 random_state=None):
+        if not (4 <= int(factors) <= LMF_MAX_FACTORS and int(factors) % 4 == 0):
+            raise ValueError(f"LMF: factors = {factors}: need a multiple of 4 in [4, {LMF_MAX_FACTORS}]")
+        if not (0 <= regularization < float("inf") and 0 < alpha < float("inf")
+                and 0 <= learning_rate < float("inf") and int(iterations) >= 0):
+            raise ValueError("LMF: need finite regularization >= 0, alpha > 0, learning_rate >= 0, iterations >= 0")
+        self.factors, self.learning_rate = int(factors), float(learning_rate)
+        self.regularization, self.alpha = float(regularization), float(alpha)
+        self.iterations, self.random_state = int(iterations), random_state
+        self.user_factors = self.item_factors = self.user_bias = self.item_bias = None
+
+    def _table(self, given, n, gen):
+        f = self.factors
+        if given is None:
+            return ((torch.rand(n, f, generator=gen) - 0.5) / f).to("cuda")
+        t = torch.as_tensor(given)
+        if tuple(t.shape) != (n, f):
+            raise ValueError(f"LMF: factors of shape {tuple(t.shape)}, expected {(n, f)}")
+        return t.to(device="cuda", dtype=torch.float32, copy=True).contiguous()
+
+    @staticmethod
+    def _bias(given, n):
+        if given is None:
+            return torch.zeros(n, dtype=torch.float32, device="cuda")
+        t = torch.as_tensor(given)
+        if tuple(t.shape) != (n,):
+            raise ValueError(f"LMF: a bias of shape {tuple(t.shape)}, expected {(n,)}")
+        return t.to(device="cuda", dtype=torch.float32, copy=True).contiguous()
+
+    def _half(self, csr, Y, by, X, bx, H, hb, D, dsum, err):
+        ptr, idx, val, n_rows, n_other = csr
+        L, f = nat.lib(), self.factors
+        nat.check(L.pinsage_lmf_dense(nat.ptr(X), nat.ptr(bx), n_rows, f, nat.ptr(Y), nat.ptr(by), n_other, f, f,
+                                      nat.ptr(D), f, nat.ptr(dsum), nat.stream_ptr()), "lmf_dense")
+        nat.check(L.pinsage_lmf_update(nat.ptr(ptr), nat.ptr(idx), nat.ptr(val), n_rows, nat.ptr(Y), nat.ptr(by),
+                                       n_other, f, nat.ptr(X), nat.ptr(bx), f, f, nat.ptr(D), f, nat.ptr(dsum),
+                                       nat.ptr(H), f, nat.ptr(hb), self.alpha, self.regularization,
+                                       self.learning_rate, nat.ptr(err), nat.stream_ptr()), "lmf_update")
+
+    def fit(self, user_items, user_factors=None, item_factors=None, user_bias=None, item_bias=None, callback=None):
+        """user_items: the (ptr, idx, val, n_users, n_items) CSR; the transpose is
+        built here.  Values are checked once on the host to be finite and > 0
+        (ValueError); a column id outside [0, n_items) raises IndexError.  Given
+        factor and bias tables are copied, not written.  ``callback(iteration,
+        self)`` runs after every iteration, the four tables set (monitoring)."""
+        nat.require_gpu()
+        ptr, idx, val, n_users, n_items = user_items
+        n_users, n_items = int(n_users), int(n_items)
+        if n_users < 1 or n_items < 1:
+            raise ValueError(f"LMF: a {n_users} x {n_items} matrix")
+        ptr = torch.as_tensor(ptr).to(device="cuda", dtype=torch.int64).contiguous()
+        idx = torch.as_tensor(idx).to(device="cuda", dtype=torch.int32).contiguous()
+        val = torch.as_tensor(val).to(device="cuda", dtype=torch.float32).contiguous()
+        if int(ptr.numel()) != n_users + 1 or int(idx.numel()) != int(val.numel()):
+            raise ValueError("LMF: the CSR arrays do not fit together")
+        if not bool((torch.isfinite(val) & (val > 0)).all()):
+            raise ValueError("LMF: values must be finite and > 0")
+        # R^T as in ALS.fit: an id out of range is clamped here and reported by the kernel below
+        rows = _csr_rows(ptr)
+        col = idx.to(torch.int64).clamp(0, n_items - 1)
+        order = torch.sort(col, stable=True).indices
+        csr_u = (ptr, idx, val, n_users, n_items)
+        csr_i = (_csr_ptr(col, n_items), rows[order].to(torch.int32).contiguous(), val[order].contiguous(),
+                 n_items, n_users)
+        gen = None if self.random_state is None else torch.Generator().manual_seed(int(self.random_state))
+        X = self._table(user_factors, n_users, gen)
+        Y = self._table(item_factors, n_items, gen)
+        bx, by = self._bias(user_bias, n_users), self._bias(item_bias, n_items)
+        f = self.factors
+        Hx, Hy = torch.zeros_like(X), torch.zeros_like(Y)
+        hbx, hby = torch.zeros_like(bx), torch.zeros_like(by)
+        D = torch.empty((max(n_users, n_items), f), dtype=torch.float32, device="cuda")
+        dsum = torch.empty(max(n_users, n_items), dtype=torch.float32, device="cuda")
+        err = torch.zeros(1, dtype=torch.int32, device="cuda")
+        self._user_items = csr_u
+        for it in range(self.iterations):
+            self._half(csr_u, Y, by, X, bx, Hx, hbx, D, dsum, err)
+            if it == 0 and int(err):
+                raise IndexError(f"LMF: item ids out of range for {n_items} items")
+            self._half(csr_i, X, bx, Y, by, Hy, hby, D, dsum, err)
+            if callback is not None:
+                self.user_factors, self.item_factors, self.user_bias, self.item_bias = X, Y, bx, by
+                callback(it, self)
+        self.user_factors, self.item_factors, self.user_bias, self.item_bias = X, Y, bx, by
+        return self
+
+    def similar_items(self, ids, N=10):
+        """(ids int64 [nq, N], scores float32 [nq, N]): the N items nearest to each
+        of ``ids`` by cosine similarity of the f latent columns of the item
+        factors, best first, on the GPU.  Biases take no part in similarity."""
+        w, nb = _knn_cosine(self.item_factors, ids, int(N))
+        return nb, w
+
+    def objective(self):
+        """lmf_objective of the fitted tables (a Python float; monitoring and tests)."""
+        return lmf_objective(self._user_items, self.user_factors, self.item_factors, self.user_bias,
+                             self.item_bias, self.regularization, self.alpha)
+
+
+class _CfModel(PredictionModel):
+    """A factorisation baseline: ``_fit`` leaves ``self.model`` with
+    ``item_factors`` and ``similar_items``."""
 
     def knn(self, nodeset, k):
         """(scores float32 [nq, k], ids int64 [nq, k]) on nodeset's device:
@@ -869,6 +1035,29 @@ class _CfALS(PredictionModel):
         out_dev = torch.as_tensor(nodeset).device
         topn_nodes, topn_scores = self.model.similar_items(nodeset, N=int(k) + 1)
         return topn_scores[:, 1:].to(out_dev), topn_nodes[:, 1:].to(out_dev)
+
+
+class _CfALS(_CfModel):
+    def __init__(self, algo="als", factors=128):
+        if algo != "als":  # the reference's "lmf" and "bpr" come from implicit too
+            raise NotImplementedError(f"algo = {algo!r}: ALS ('als') is the only algorithm of these classes; "
+                                      "logistic MF is ColTrackLMF / TrackTrackLMF")
+        self.algo = algo
+        self.factors = factors
+
+    def _fit(self, mat):
+        self.model = ALS(factors=self.factors)
+        self.model.fit(mat)
+
+
+class _CfLMF(_CfModel):
+    def __init__(self, factors=128):
+        self.algo = "lmf"
+        self.factors = factors
+
+    def _fit(self, mat):
+        self.model = LMF(factors=self.factors)
+        self.model.fit(mat)
 
 
 class TrackTrackCF(_CfALS):
@@ -884,6 +1073,26 @@ class TrackTrackCF(_CfALS):
 class ColTrackCF(_CfALS):
     """Matrix factorisation of the collection-track membership matrix
     (baselines.py:489-514), by ALS."""
+
+    def train(self, g, ids, train_set, test_set, features):
+        self.ids = ids
+        self.n = len(ids)
+        self._fit(to_col_track_matrix(g, ids))
+
+
+class TrackTrackLMF(_CfLMF):
+    """TrackTrackCF with the fit replaced by logistic matrix factorisation
+    (the reference's algo="lmf"; ``LMF`` above)."""
+
+    def train(self, g, ids, train_set, test_set, features):
+        self.ids = ids
+        self.n = len(ids)
+        self._fit(to_track_track_matrix(ids, train_set))
+
+
+class ColTrackLMF(_CfLMF):
+    """ColTrackCF with the fit replaced by logistic matrix factorisation
+    (the reference's algo="lmf"; ``LMF`` above)."""
 
     def train(self, g, ids, train_set, test_set, features):
         self.ids = ids
@@ -960,4 +1169,5 @@ __all__ = ["PRECOMP_K", "PredictionModel", "EmbeddingModel", "cosine_sim_ab", "k
            "coverage", "average_degree", "degree_dist", "beyond_accuracy", "compute_beyond_accuracy_table",
            "JaccardFast", "Random", "low_co_accuracy", "low_co_accuracy_from_ranks", "LazyKnnDict",
            "compute_results_table", "ALS_MAX_FACTORS", "ALS", "als_loss", "to_col_track_matrix",
-           "to_track_track_matrix", "ColTrackCF", "TrackTrackCF"]
+           "to_track_track_matrix", "ColTrackCF", "TrackTrackCF", "LMF_MAX_FACTORS", "LMF", "lmf_objective",
+           "ColTrackLMF", "TrackTrackLMF"]

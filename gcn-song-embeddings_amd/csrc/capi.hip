@@ -10,6 +10,7 @@
 #include "../../include/pinsage_hip.h"
 #include "aggw.h"
 #include "als.h"
+#include "lmf.h"
 #include "capi.h"
 #include "conv.h"
 #include "cooc.h"
@@ -769,6 +770,23 @@ int pinsage_als_half(const int64_t* ptr, const int32_t* idx, const float* val, i
                      int64_t cg_steps, int* err, void* stream) {
   return launch_als_half(ptr, idx, val, n_rows, Y, n_other, ldy, X, ldx, f, G, alpha, cg_steps, err,
                          (hipStream_t)stream);
+}
+
+int64_t pinsage_lmf_row_block(void) { return lmf_row_block(); }
+
+int64_t pinsage_lmf_long_row(void) { return lmf_long_row(); }
+
+int pinsage_lmf_dense(const float* X, const float* bx, int64_t n_rows, int64_t ldx, const float* Y, const float* by,
+                      int64_t n_other, int64_t ldy, int64_t f, float* D, int64_t ldd, float* dsum, void* stream) {
+  return launch_lmf_dense(X, bx, n_rows, ldx, Y, by, n_other, ldy, f, D, ldd, dsum, (hipStream_t)stream);
+}
+
+int pinsage_lmf_update(const int64_t* ptr, const int32_t* idx, const float* val, int64_t n_rows, const float* Y,
+                       const float* by, int64_t n_other, int64_t ldy, float* X, float* bx, int64_t ldx, int64_t f,
+                       const float* D, int64_t ldd, const float* dsum, float* H, int64_t ldh, float* hb,
+                       float alpha, float reg, float lr, int* err, void* stream) {
+  return launch_lmf_update(ptr, idx, val, n_rows, Y, by, n_other, ldy, X, bx, ldx, f, D, ldd, dsum, H, ldh, hb,
+                           alpha, reg, lr, err, (hipStream_t)stream);
 }
 
 int64_t pinsage_knn_scratch_bytes(int64_t n, int64_t batch_rows) {

@@ -853,6 +853,60 @@ int pinsage_als_half(const int64_t* ptr, const int32_t* idx, const float* val, i
                      int64_t n_other, int64_t ldy, float* X, int64_t ldx, int64_t f, const float* G, float alpha,
                      int64_t cg_steps, int* err, void* stream);
 
+/* ------------------------------------------------------------------ logistic matrix factorisation
+ * Johnson, "Logistic Matrix Factorization for Implicit Feedback Data" (2014):
+ * the algo="lmf" the reference takes from the implicit package.  The arithmetic
+ * below is this project's definition, the paper's full-gradient AdaGrad ascent
+ * without negative sampling; parity with that package's numbers is not claimed.
+ *
+ * R [n_users, n_items] is a CSR with values r > 0, c = alpha r.  Tables X
+ * [n_users, f], Y [n_items, f], biases bx [n_users], by [n_items]; the score is
+ * s_ui = x_u . y_i + bx_u + by_i.  The objective to MAXIMISE is
+ *   L = sum_obs c s - sum_obs (1 + c) softplus(s) - sum_unobs softplus(s)
+ *       - (reg / 2)(|X|^2 + |Y|^2)                     (biases not regularised)
+ * One iteration updates every user row from (Y, by), then every item row from
+ * the new (X, bx) with R^T as the CSR.  A half-iteration is Jacobi: every row
+ * reads the old tables only.  Per row u, in fp32:
+ *   D    = sum_all i sig(s_ui) y_i         dsum = sum_all i sig(s_ui)
+ *   w_i  = c_ui sig(-s_ui)  for observed i       (= c (1 - sig(s)), no cancellation)
+ *   g    = sum_obs w_i y_i - D - reg x_u   gb = sum_obs w_i - dsum
+ *   h   += g^2 (elementwise)               hb += gb^2    (AdaGrad, start at 0)
+ *   x_u += lr g / sqrt(1e-6 + h)           bx_u += lr gb / sqrt(1e-6 + hb)
+ * sig is evaluated stably: for s >= 0 it is 1 / (1 + e^-s), otherwise
+ * e^s / (1 + e^s); it is never NaN or Inf for finite s.
+ *
+ * pinsage_lmf_dense: D f32 [n_rows][ldd] and dsum f32 [n_rows] for every row of
+ * X, bx against all of Y f32 [n_other][ldy], by.  One fused kernel on the
+ * exact-f32 MFMA: no n_rows x n_other buffer exists.  A workgroup owns
+ * pinsage_lmf_row_block() rows and walks all items in ascending order; no
+ * atomics, the same bits on every run, and the bits of row u depend on x_u,
+ * bx_u, Y and by only.  Columns [f, ld) are neither read nor written.
+ *
+ * pinsage_lmf_update: the rest of the recurrence, in place on X, bx, H f32
+ * [n_rows][ldh], hb, from D and dsum of the old tables; CSR as pinsage_als_half.
+ * s_i is recomputed for the observed cells from the old x_u as (x . y_i + bx) +
+ * by_i; g = fma(-reg, x, sum - D), h = fma(g, g, h).  A row of at most
+ * pinsage_lmf_long_row() items is taken by one wave, its item sums in CSR
+ * order; a longer one by a whole workgroup, wave w summing the 64-item groups
+ * w, w + 8, ... and the 8 partial sums added in wave order.  The form depends on
+ * the row's length alone.  lr == 0 leaves X and bx bit for bit and still updates
+ * H and hb.
+ *
+ * All pointers are device memory.  err (nullable): as pinsage_als_half.  A
+ * refused call (PINSAGE_ERR_ARG: f outside [4, 128] or f % 4 != 0; a leading
+ * dimension below f or not a multiple of 4; a table not 16-byte aligned or
+ * null; a null bias, dsum or hb; alpha <= 0, reg < 0, lr < 0 or any not finite;
+ * a count above INT32_MAX; n_other < 1) returns before any launch and leaves
+ * every output untouched.  n_rows == 0 is accepted and launches nothing. */
+int64_t pinsage_lmf_row_block(void);
+int64_t pinsage_lmf_long_row(void);
+int pinsage_lmf_dense(const float* X, const float* bx, int64_t n_rows, int64_t ldx, const float* Y, const float* by,
+                      int64_t n_other, int64_t ldy, int64_t f, float* D, int64_t ldd, float* dsum, void* stream);
+int pinsage_lmf_update(const int64_t* ptr, const int32_t* idx, const float* val, int64_t n_rows, const float* Y,
+                       const float* by, int64_t n_other, int64_t ldy, float* X, float* bx, int64_t ldx, int64_t f,
+                       const float* D, int64_t ldd, const float* dsum, float* H, int64_t ldh, float* hb,
+                       float alpha, float reg, float lr, int* err, void* stream);
+
 /* ------------------------------------------------------------------ train-step engine
  * PinSageModel.forward / PinSage.train_batch (pinsage_model.py:246-265,
  * pinsage_training.py:181-214) with device-resident sizes.  Parameters live in
