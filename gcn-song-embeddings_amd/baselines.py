@@ -83,6 +83,11 @@ def cosine_sim_ab(a, b, eps=1e-16):
     return dot_prod / (lengths_mat + eps)
 
 
+def _batch_rows(nq, n):
+    """How many of nq query rows, n scores each, one batch holds in KNN_SCRATCH_BYTES (read now)."""
+    return max(1, min(nq, (KNN_SCRATCH_BYTES - 8 * n) // max(1, 4 * n)))
+
+
 def _knn_cosine(emb, q, k_total, eps=1e-16):
     """Top-k_total cosine neighbours of rows q of emb (HIP: MFMA dot products +
     per-row radix select), sorted descending: (w f32 [nq, k], n i64 [nq, k])."""
@@ -102,8 +107,7 @@ def _knn_cosine(emb, q, k_total, eps=1e-16):
     w = torch.empty((nq, k_total), dtype=torch.float32, device="cuda")
     nb = torch.empty((nq, k_total), dtype=torch.int64, device="cuda")
     L = nat.lib()
-    rows = max(1, min(nq, (KNN_SCRATCH_BYTES - 8 * n) // max(1, 4 * n)))
-    nbytes = L.pinsage_knn_scratch_bytes(n, rows)
+    nbytes = L.pinsage_knn_scratch_bytes(n, _batch_rows(nq, n))
     scratch = torch.empty(nbytes, dtype=torch.uint8, device="cuda")
     nat.check(L.pinsage_knn_cosine(nat.ptr(e), n, d, d, nat.ptr(qd), nq, int(k_total), float(eps),
                                    nat.ptr(scratch), nbytes, nat.ptr(w), nat.ptr(nb),
@@ -177,8 +181,7 @@ def rank_from_emb(emb, queries, targets, eps=1e-16):
     nu = int(rows_q.numel())
     out = torch.empty(npairs, dtype=torch.int64, device="cuda")
     L = nat.lib()
-    rows = max(1, min(nu, (KNN_SCRATCH_BYTES - 8 * n) // max(1, 4 * n)))
-    nbytes = L.pinsage_rank_scratch_bytes(n, rows)
+    nbytes = L.pinsage_rank_scratch_bytes(n, _batch_rows(nu, n))
     scratch = torch.empty(nbytes, dtype=torch.uint8, device="cuda")
     nat.check(L.pinsage_rank_cosine(nat.ptr(e), n, d, d, nat.ptr(rows_q), nu, nat.ptr(grp_ptr),
                                     nat.ptr(tsorted), npairs, float(eps), nat.ptr(scratch), nbytes,
@@ -675,8 +678,7 @@ class JaccardFast(PredictionModel):
         nb = torch.empty((nq, k), dtype=torch.int64, device="cuda")
         if nq:
             L = nat.lib()
-            rows = max(1, min(nq, (KNN_SCRATCH_BYTES - 8 * n) // max(1, 4 * n)))
-            nbytes = L.pinsage_cooc_scratch_bytes(n, rows)
+            nbytes = L.pinsage_cooc_scratch_bytes(n, _batch_rows(nq, n))
             scratch = torch.empty(nbytes, dtype=torch.uint8, device="cuda")
             err = torch.zeros(1, dtype=torch.int32, device="cuda")
             nat.check(L.pinsage_cooc_jaccard(*self._csr_args(), nat.ptr(qd), nq, k, nat.ptr(scratch), nbytes,
@@ -692,7 +694,7 @@ class JaccardFast(PredictionModel):
 # (ptr int64 [n_rows + 1], idx int32, val float32, n_rows, n_cols), rows with
 # ascending column ids and no cell twice, on the GPU unless ``device`` says
 # otherwise (the builders and als_loss are plain torch and run anywhere).
-ALS_MAX_FACTORS = 128  # kAlsMaxF (csrc/als.hip)
+ALS_MAX_FACTORS = LMF_MAX_FACTORS = 128  # kRowMaxF (csrc/rowplan.h)
 
 
 def to_col_track_matrix(g, ids, device=None):
@@ -731,6 +733,71 @@ def _csr_rows(ptr):
     return torch.repeat_interleave(torch.arange(n, dtype=torch.int64, device=ptr.device), ptr[1:] - ptr[:-1])
 
 
+def _csr_transpose(ptr, idx, val, n_rows, n_cols):
+    """R^T as such a tuple: a stable sort by column keeps the rows ascending
+    within a column.  An id out of range is clamped into [0, n_cols) (the
+    kernels report it)."""
+    col = idx.to(torch.int64).clamp(0, n_cols - 1)
+    order = torch.sort(col, stable=True).indices
+    return (_csr_ptr(col, n_cols), _csr_rows(ptr)[order].to(torch.int32).contiguous(), val[order].contiguous(),
+            n_cols, n_rows)
+
+
+class _RowFit:
+    """What ALS and LMF share: the factor tables, the intake of the matrix and
+    similar_items.  ``_who`` prefixes the error texts."""
+
+    def __init__(self, factors, random_state):
+        if not (4 <= int(factors) <= ALS_MAX_FACTORS and int(factors) % 4 == 0):
+            raise ValueError(f"{self._who}: factors = {factors}: need a multiple of 4 in [4, {ALS_MAX_FACTORS}]")
+        self.factors, self.random_state = int(factors), random_state
+        self.user_factors = self.item_factors = None
+
+    def _table(self, given, n, gen):
+        f = self.factors
+        if given is None:
+            return ((torch.rand(n, f, generator=gen) - 0.5) / f).to("cuda")
+        t = torch.as_tensor(given)
+        if tuple(t.shape) != (n, f):
+            raise ValueError(f"{self._who}: factors of shape {tuple(t.shape)}, expected {(n, f)}")
+        return t.to(device="cuda", dtype=torch.float32, copy=True).contiguous()
+
+    def _intake(self, user_items, user_factors, item_factors):
+        """(R, R^T, X, Y, err): the checked CSR on the GPU and its transpose, the
+        two factor tables (drawn users first, then items) and the zeroed device
+        word that a half-iteration sets on a column id out of range."""
+        nat.require_gpu()
+        ptr, idx, val, n_users, n_items = user_items
+        n_users, n_items = int(n_users), int(n_items)
+        if n_users < 1 or n_items < 1:
+            raise ValueError(f"{self._who}: a {n_users} x {n_items} matrix")
+        ptr = torch.as_tensor(ptr).to(device="cuda", dtype=torch.int64).contiguous()
+        idx = torch.as_tensor(idx).to(device="cuda", dtype=torch.int32).contiguous()
+        val = torch.as_tensor(val).to(device="cuda", dtype=torch.float32).contiguous()
+        if int(ptr.numel()) != n_users + 1 or int(idx.numel()) != int(val.numel()):
+            raise ValueError(f"{self._who}: the CSR arrays do not fit together")
+        if not bool((torch.isfinite(val) & (val > 0)).all()):
+            raise ValueError(f"{self._who}: values must be finite and > 0")
+        self._user_items = csr_u = (ptr, idx, val, n_users, n_items)
+        gen = None if self.random_state is None else torch.Generator().manual_seed(int(self.random_state))
+        X = self._table(user_factors, n_users, gen)
+        Y = self._table(item_factors, n_items, gen)
+        return csr_u, _csr_transpose(*csr_u), X, Y, torch.zeros(1, dtype=torch.int32, device="cuda")
+
+    def _ids_checked(self, err):
+        """After the first user half: it has met every column id."""
+        if int(err):
+            raise IndexError(f"{self._who}: item ids out of range for {self._user_items[4]} items")
+
+    def similar_items(self, ids, N=10):
+        """(ids int64 [nq, N], scores float32 [nq, N]): the N items nearest to each
+        of ``ids`` by cosine similarity of the f latent columns of the item
+        factors, best first (the query itself comes first unless another item
+        ties it), on the GPU.  Biases, where there are any, take no part."""
+        w, nb = _knn_cosine(self.item_factors, ids, int(N))
+        return nb, w
+
+
 def als_loss(user_items, user_factors, item_factors, regularization, alpha=1.0):
     """The ALS objective  sum_observed c (1 - x.y)^2 + sum_unobserved (x.y)^2 +
     reg (|X|^2 + |Y|^2),  c = alpha r,  in float64 on the factors' device without
@@ -748,7 +815,7 @@ def als_loss(user_items, user_factors, item_factors, regularization, alpha=1.0):
     return float(total + float(regularization) * ((X * X).sum() + (Y * Y).sum()))
 
 
-class ALS:
+class ALS(_RowFit):
     """Implicit-feedback alternating least squares (Hu, Koren, Volinsky) with the
     conjugate-gradient row solve of Takacs et al., on the kernels of
     csrc/als.hip: what the reference takes from
@@ -777,23 +844,14 @@ class ALS:
     then items, from a torch.Generator seeded with ``random_state`` or, with
     None, from torch's global generator."""
 
+    _who = "ALS"
+
     def __init__(self, factors=128, regularization=0.01, alpha=1.0, iterations=15, cg_steps=3, random_state=None):
-        if not (4 <= int(factors) <= ALS_MAX_FACTORS and int(factors) % 4 == 0):
-            raise ValueError(f"ALS: factors = {factors}: need a multiple of 4 in [4, {ALS_MAX_FACTORS}]")
+        super().__init__(factors, random_state)
         if not (regularization > 0 and alpha > 0 and int(iterations) >= 0 and int(cg_steps) >= 0):
             raise ValueError("ALS: need regularization > 0, alpha > 0, iterations >= 0, cg_steps >= 0")
-        self.factors, self.regularization, self.alpha = int(factors), float(regularization), float(alpha)
-        self.iterations, self.cg_steps, self.random_state = int(iterations), int(cg_steps), random_state
-        self.user_factors = self.item_factors = None
-
-    def _table(self, given, n, gen):
-        f = self.factors
-        if given is None:
-            return ((torch.rand(n, f, generator=gen) - 0.5) / f).to("cuda")
-        t = torch.as_tensor(given)
-        if tuple(t.shape) != (n, f):
-            raise ValueError(f"ALS: factors of shape {tuple(t.shape)}, expected {(n, f)}")
-        return t.to(device="cuda", dtype=torch.float32, copy=True).contiguous()
+        self.regularization, self.alpha = float(regularization), float(alpha)
+        self.iterations, self.cg_steps = int(iterations), int(cg_steps)
 
     def _half(self, csr, Y, X, G, err):
         ptr, idx, val, n_rows, n_other = csr
@@ -809,53 +867,21 @@ class ALS:
         built here.  Values are checked once on the host to be finite and > 0
         (ValueError); a column id outside [0, n_items) raises IndexError.  Given
         factor tables are copied, not written."""
-        nat.require_gpu()
-        ptr, idx, val, n_users, n_items = user_items
-        n_users, n_items = int(n_users), int(n_items)
-        if n_users < 1 or n_items < 1:
-            raise ValueError(f"ALS: a {n_users} x {n_items} matrix")
-        ptr = torch.as_tensor(ptr).to(device="cuda", dtype=torch.int64).contiguous()
-        idx = torch.as_tensor(idx).to(device="cuda", dtype=torch.int32).contiguous()
-        val = torch.as_tensor(val).to(device="cuda", dtype=torch.float32).contiguous()
-        if int(ptr.numel()) != n_users + 1 or int(idx.numel()) != int(val.numel()):
-            raise ValueError("ALS: the CSR arrays do not fit together")
-        if not bool((torch.isfinite(val) & (val > 0)).all()):
-            raise ValueError("ALS: values must be finite and > 0")
-        # R^T: a stable sort by column keeps the rows ascending within a column;
-        # an id out of range is clamped here and reported by the kernel below
-        rows = _csr_rows(ptr)
-        col = idx.to(torch.int64).clamp(0, n_items - 1)
-        order = torch.sort(col, stable=True).indices
-        csr_u = (ptr, idx, val, n_users, n_items)
-        csr_i = (_csr_ptr(col, n_items), rows[order].to(torch.int32).contiguous(), val[order].contiguous(),
-                 n_items, n_users)
-        gen = None if self.random_state is None else torch.Generator().manual_seed(int(self.random_state))
-        X = self._table(user_factors, n_users, gen)
-        Y = self._table(item_factors, n_items, gen)
+        csr_u, csr_i, X, Y, err = self._intake(user_items, user_factors, item_factors)
         G = torch.empty((self.factors, self.factors), dtype=torch.float32, device="cuda")
-        err = torch.zeros(1, dtype=torch.int32, device="cuda")
         for it in range(self.iterations):
             self._half(csr_u, Y, X, G, err)
-            if it == 0 and int(err):
-                raise IndexError(f"ALS: item ids out of range for {n_items} items")
+            if it == 0:
+                self._ids_checked(err)
             self._half(csr_i, X, Y, G, err)
-        self._user_items = csr_u
         self.user_factors, self.item_factors = X, Y
         return self
-
-    def similar_items(self, ids, N=10):
-        """(ids int64 [nq, N], scores float32 [nq, N]): the N items nearest to each
-        of ``ids`` by cosine similarity of the item factors, best first (the
-        query itself comes first unless another item ties it), on the GPU."""
-        w, nb = _knn_cosine(self.item_factors, ids, int(N))
-        return nb, w
 
     def loss(self):
         """als_loss of the fitted factors (a Python float; monitoring and tests)."""
         return als_loss(self._user_items, self.user_factors, self.item_factors, self.regularization, self.alpha)
 
 
-LMF_MAX_FACTORS = 128  # kLmfMaxF (csrc/lmf.hip)
 _LMF_CELLS = 1 << 24  # dense cells of lmf_objective formed at once
 
 
@@ -891,7 +917,7 @@ def lmf_objective(user_items, user_factors, item_factors, user_bias, item_bias, 
     return float(total - 0.5 * float(regularization) * ((X * X).sum() + (Y * Y).sum()))
 
 
-class LMF:
+class LMF(_RowFit):
     """Logistic matrix factorisation (Johnson, "Logistic Matrix Factorization for
     Implicit Feedback Data", 2014) on the kernels of csrc/lmf.hip: what the
     reference takes from implicit's LogisticMatrixFactorization with
@@ -924,26 +950,17 @@ class LMF:
     ``random_state`` or, with None, from torch's global generator; biases and
     accumulators start at zero."""
 
+    _who = "LMF"
+
     def __init__(self, factors=128, learning_rate=0.1, regularization=0.6, alpha=1.0, iterations=30,
                  random_state=None):
-        if not (4 <= int(factors) <= LMF_MAX_FACTORS and int(factors) % 4 == 0):
-            raise ValueError(f"LMF: factors = {factors}: need a multiple of 4 in [4, {LMF_MAX_FACTORS}]")
+        super().__init__(factors, random_state)
         if not (0 <= regularization < float("inf") and 0 < alpha < float("inf")
                 and 0 <= learning_rate < float("inf") and int(iterations) >= 0):
             raise ValueError("LMF: need finite regularization >= 0, alpha > 0, learning_rate >= 0, iterations >= 0")
-        self.factors, self.learning_rate = int(factors), float(learning_rate)
-        self.regularization, self.alpha = float(regularization), float(alpha)
-        self.iterations, self.random_state = int(iterations), random_state
-        self.user_factors = self.item_factors = self.user_bias = self.item_bias = None
-
-    def _table(self, given, n, gen):
-        f = self.factors
-        if given is None:
-            return ((torch.rand(n, f, generator=gen) - 0.5) / f).to("cuda")
-        t = torch.as_tensor(given)
-        if tuple(t.shape) != (n, f):
-            raise ValueError(f"LMF: factors of shape {tuple(t.shape)}, expected {(n, f)}")
-        return t.to(device="cuda", dtype=torch.float32, copy=True).contiguous()
+        self.learning_rate, self.regularization, self.alpha = float(learning_rate), float(regularization), float(alpha)
+        self.iterations = int(iterations)
+        self.user_bias = self.item_bias = None
 
     @staticmethod
     def _bias(given, n):
@@ -970,53 +987,23 @@ class LMF:
         (ValueError); a column id outside [0, n_items) raises IndexError.  Given
         factor and bias tables are copied, not written.  ``callback(iteration,
         self)`` runs after every iteration, the four tables set (monitoring)."""
-        nat.require_gpu()
-        ptr, idx, val, n_users, n_items = user_items
-        n_users, n_items = int(n_users), int(n_items)
-        if n_users < 1 or n_items < 1:
-            raise ValueError(f"LMF: a {n_users} x {n_items} matrix")
-        ptr = torch.as_tensor(ptr).to(device="cuda", dtype=torch.int64).contiguous()
-        idx = torch.as_tensor(idx).to(device="cuda", dtype=torch.int32).contiguous()
-        val = torch.as_tensor(val).to(device="cuda", dtype=torch.float32).contiguous()
-        if int(ptr.numel()) != n_users + 1 or int(idx.numel()) != int(val.numel()):
-            raise ValueError("LMF: the CSR arrays do not fit together")
-        if not bool((torch.isfinite(val) & (val > 0)).all()):
-            raise ValueError("LMF: values must be finite and > 0")
-        # R^T as in ALS.fit: an id out of range is clamped here and reported by the kernel below
-        rows = _csr_rows(ptr)
-        col = idx.to(torch.int64).clamp(0, n_items - 1)
-        order = torch.sort(col, stable=True).indices
-        csr_u = (ptr, idx, val, n_users, n_items)
-        csr_i = (_csr_ptr(col, n_items), rows[order].to(torch.int32).contiguous(), val[order].contiguous(),
-                 n_items, n_users)
-        gen = None if self.random_state is None else torch.Generator().manual_seed(int(self.random_state))
-        X = self._table(user_factors, n_users, gen)
-        Y = self._table(item_factors, n_items, gen)
+        csr_u, csr_i, X, Y, err = self._intake(user_items, user_factors, item_factors)
+        n_users, n_items = csr_u[3:]
         bx, by = self._bias(user_bias, n_users), self._bias(item_bias, n_items)
-        f = self.factors
         Hx, Hy = torch.zeros_like(X), torch.zeros_like(Y)
         hbx, hby = torch.zeros_like(bx), torch.zeros_like(by)
-        D = torch.empty((max(n_users, n_items), f), dtype=torch.float32, device="cuda")
+        D = torch.empty((max(n_users, n_items), self.factors), dtype=torch.float32, device="cuda")
         dsum = torch.empty(max(n_users, n_items), dtype=torch.float32, device="cuda")
-        err = torch.zeros(1, dtype=torch.int32, device="cuda")
-        self._user_items = csr_u
         for it in range(self.iterations):
             self._half(csr_u, Y, by, X, bx, Hx, hbx, D, dsum, err)
-            if it == 0 and int(err):
-                raise IndexError(f"LMF: item ids out of range for {n_items} items")
+            if it == 0:
+                self._ids_checked(err)
             self._half(csr_i, X, bx, Y, by, Hy, hby, D, dsum, err)
             if callback is not None:
                 self.user_factors, self.item_factors, self.user_bias, self.item_bias = X, Y, bx, by
                 callback(it, self)
         self.user_factors, self.item_factors, self.user_bias, self.item_bias = X, Y, bx, by
         return self
-
-    def similar_items(self, ids, N=10):
-        """(ids int64 [nq, N], scores float32 [nq, N]): the N items nearest to each
-        of ``ids`` by cosine similarity of the f latent columns of the item
-        factors, best first, on the GPU.  Biases take no part in similarity."""
-        w, nb = _knn_cosine(self.item_factors, ids, int(N))
-        return nb, w
 
     def objective(self):
         """lmf_objective of the fitted tables (a Python float; monitoring and tests)."""
@@ -1025,8 +1012,14 @@ class LMF:
 
 
 class _CfModel(PredictionModel):
-    """A factorisation baseline: ``_fit`` leaves ``self.model`` with
-    ``item_factors`` and ``similar_items``."""
+    """A factorisation baseline: ``train`` fits a ``_Fit`` (ALS or LMF) to the
+    ``_matrix`` of the training data and leaves it in ``self.model``."""
+
+    def train(self, g, ids, train_set, test_set, features):
+        self.ids = ids
+        self.n = len(ids)
+        self.model = self._Fit(factors=self.factors)
+        self.model.fit(self._matrix(g, ids, train_set))
 
     def knn(self, nodeset, k):
         """(scores float32 [nq, k], ids int64 [nq, k]) on nodeset's device:
@@ -1038,6 +1031,8 @@ class _CfModel(PredictionModel):
 
 
 class _CfALS(_CfModel):
+    _Fit = ALS
+
     def __init__(self, algo="als", factors=128):
         if algo != "als":  # the reference's "lmf" and "bpr" come from implicit too
             raise NotImplementedError(f"algo = {algo!r}: ALS ('als') is the only algorithm of these classes; "
@@ -1045,59 +1040,43 @@ class _CfALS(_CfModel):
         self.algo = algo
         self.factors = factors
 
-    def _fit(self, mat):
-        self.model = ALS(factors=self.factors)
-        self.model.fit(mat)
-
 
 class _CfLMF(_CfModel):
+    _Fit = LMF
+
     def __init__(self, factors=128):
         self.algo = "lmf"
         self.factors = factors
 
-    def _fit(self, mat):
-        self.model = LMF(factors=self.factors)
-        self.model.fit(mat)
+
+class _TrackTrack:
+    def _matrix(self, g, ids, train_set):
+        return to_track_track_matrix(ids, train_set)
 
 
-class TrackTrackCF(_CfALS):
+class _ColTrack:
+    def _matrix(self, g, ids, train_set):
+        return to_col_track_matrix(g, ids)
+
+
+class TrackTrackCF(_TrackTrack, _CfALS):
     """Matrix factorisation of the track-track co-occurrence matrix of the
     training positives (baselines.py:458-487), by ALS."""
 
-    def train(self, g, ids, train_set, test_set, features):
-        self.ids = ids
-        self.n = len(ids)
-        self._fit(to_track_track_matrix(ids, train_set))
 
-
-class ColTrackCF(_CfALS):
+class ColTrackCF(_ColTrack, _CfALS):
     """Matrix factorisation of the collection-track membership matrix
     (baselines.py:489-514), by ALS."""
 
-    def train(self, g, ids, train_set, test_set, features):
-        self.ids = ids
-        self.n = len(ids)
-        self._fit(to_col_track_matrix(g, ids))
 
-
-class TrackTrackLMF(_CfLMF):
+class TrackTrackLMF(_TrackTrack, _CfLMF):
     """TrackTrackCF with the fit replaced by logistic matrix factorisation
     (the reference's algo="lmf"; ``LMF`` above)."""
 
-    def train(self, g, ids, train_set, test_set, features):
-        self.ids = ids
-        self.n = len(ids)
-        self._fit(to_track_track_matrix(ids, train_set))
 
-
-class ColTrackLMF(_CfLMF):
+class ColTrackLMF(_ColTrack, _CfLMF):
     """ColTrackCF with the fit replaced by logistic matrix factorisation
     (the reference's algo="lmf"; ``LMF`` above)."""
-
-    def train(self, g, ids, train_set, test_set, features):
-        self.ids = ids
-        self.n = len(ids)
-        self._fit(to_col_track_matrix(g, ids))
 
 
 class Random(PredictionModel):

@@ -9,32 +9,23 @@
 // ascending) and the 16 partial sums are added in wave order: a fixed order, no
 // atomics, and G[a][b] and G[b][a] are the same bits.
 //
-// als_half_kernel: one half-iteration.  A workgroup of kAlsWaves waves stages G
-// in LDS once (64 KiB at f = 128: two workgroups per CU) and walks kAlsBlocks
-// blocks of kAlsWaves consecutive rows.  A lane owns columns 2 lane and 2 lane + 1 of
-// every f-vector (x, r, p, Ap, a gathered y_i), so a row of Y is one 8-byte load
-// per lane, G p is f steps of one LDS read (row k of G, conflict-free) against
-// p[k] read from its lane, and a dot product is a lane product and the xor
-// butterfly, whose result is the same in every lane.
-//   Ordinary row (at most kAlsLongRow items): one wave, items in CSR order,
-//   kAlsRows rows' loads in flight per step.
-//   Long row: the whole workgroup.  Every wave carries the same x, r, p (same
-//   inputs, same instructions: same bits); only the item sums are split, wave w
-//   taking the 64-item groups w, w + kAlsWaves, ... of the row, and the
-//   kAlsWaves partial sums meet in LDS and are added in wave order.
-// Which form a row takes depends on its length alone, and neither form's sum
-// order depends on the grid, so the output bits depend only on the inputs.
+// als_half_kernel: one half-iteration on the row plan of rowplan.h (the item
+// walk, the long row's wave-order sum, the dispatch of a block of rows).  A
+// workgroup stages G in LDS once (64 KiB at f = 128: two workgroups per CU) and
+// walks kAlsBlocks blocks of rows.  The lane's two columns hold x, r, p, Ap and
+// a gathered y_i alike: G p is f steps of one LDS read (row k of G,
+// conflict-free) against p[k] read from its lane, and a dot product is a lane
+// product and the xor butterfly, whose result is the same in every lane.  In a
+// long row every wave carries the same x, r, p (same inputs, same instructions:
+// same bits); only the item sums are split.
 #include <algorithm>
 
 #include "als.h"
+#include "rowplan.h"
 
 namespace ps {
 
-constexpr int kAlsWaves = 8;       // waves (= ordinary rows) per workgroup and block of rows
-constexpr int kAlsBlocks = 4;      // blocks of rows per workgroup: G is staged once per 32 rows
-constexpr int kAlsRows = 8;        // item rows whose loads are in flight per step
-constexpr int kAlsLongRow = 512;   // a row above this many items is taken by the workgroup
-constexpr int kAlsMaxF = 128;      // 2 columns per lane
+constexpr int kAlsBlocks = 4;       // blocks of rows per workgroup: G is staged once per 32 rows
 constexpr float kAlsTiny = 1e-20f;  // a squared residual below this ends the row's solve
 
 constexpr int kGramTile = 8;
@@ -64,22 +55,14 @@ __global__ __launch_bounds__(64 * kGramSlices) void gram_kernel(const float* __r
 
 struct AlsArgs {
   const int64_t* ptr;
-  const int32_t* idx;
-  const float* val;
   int64_t n_rows;
-  const float* Y;
-  int64_t n_other, ldy;
+  RowItems I;  // by unused
   float* X;
   int64_t ldx;
   int f;
-  float alpha;
   int steps;
-  int* err;
 };
 
-__device__ __forceinline__ float2 als_ld2(const float* p, bool on) {
-  return on ? *reinterpret_cast<const float2*>(p) : make_float2(0.f, 0.f);
-}
 __device__ __forceinline__ float als_dot(float2 a, float2 b) { return wave_sum(fmaf(a.x, b.x, a.y * b.y)); }
 
 // (G v)[c] = sum_k G[k][c] v[k], k ascending, for the lane's two columns
@@ -98,70 +81,25 @@ __device__ __forceinline__ float2 als_gv(const float* __restrict__ Gs, int f, in
   return acc;
 }
 
-// sum over the items [b, e) taken in groups of 64 (group g0, g0 + gs, ...) of
+// sum over the row's items [b, e) of
 //   RES:  (c - (c - 1) (y . v)) y      else:  (c - 1) (y . v) y,     c = alpha val
-template <bool RES>
-__device__ __forceinline__ float2 als_items(const AlsArgs& A, int64_t b, int64_t e, int g0, int gs, int lane, int c0,
-                                            bool on, float2 v) {
-  float2 acc = make_float2(0.f, 0.f);
-  for (int64_t j0 = b + (int64_t)g0 * 64; j0 < e; j0 += (int64_t)gs * 64) {  // wave-uniform
-    const int m = (int)min<int64_t>(64, e - j0);
-    int id = 0;
-    float c = 0.f;
-    if (lane < m) {
-      id = A.idx[j0 + lane];
-      if (id < 0 || id >= A.n_other) {  // callers validate; clamp so that no access strays
-        if (A.err) atomicExch(A.err, 1);
-        id = 0;
-      }
-      c = A.alpha * A.val[j0 + lane];
-    }
-    auto add = [&](float2 y, float cu) __attribute__((always_inline)) {
-      const float d = als_dot(y, v);
-      const float w = RES ? cu - (cu - 1.f) * d : (cu - 1.f) * d;
-      acc.x = fmaf(w, y.x, acc.x);
-      acc.y = fmaf(w, y.y, acc.y);
-    };
-    int u = 0;
-    for (; u + kAlsRows <= m; u += kAlsRows) {
-      float2 y[kAlsRows];
-      float cu[kAlsRows];
-#pragma unroll
-      for (int r = 0; r < kAlsRows; ++r) {
-        y[r] = als_ld2(A.Y + (int64_t)__shfl(id, u + r, 64) * A.ldy + c0, on);
-        cu[r] = __shfl(c, u + r, 64);
-      }
-#pragma unroll
-      for (int r = 0; r < kAlsRows; ++r) add(y[r], cu[r]);
-    }
-    for (; u < m; ++u) add(als_ld2(A.Y + (int64_t)__shfl(id, u, 64) * A.ldy + c0, on), __shfl(c, u, 64));
-  }
-  return acc;
-}
-
 // LONG: called by every wave of the workgroup with the same v; barriers inside.
 template <bool RES, bool LONG>
 __device__ __forceinline__ float2 als_sum(const AlsArgs& A, int64_t b, int64_t e, int lane, int wv, int c0, bool on,
                                           float* __restrict__ part, float2 v) {
-  if constexpr (!LONG) {
-    return als_items<RES>(A, b, e, 0, 1, lane, c0, on, v);
-  } else {
-    const float2 mine = als_items<RES>(A, b, e, wv, kAlsWaves, lane, c0, on, v);
-    if (on) *reinterpret_cast<float2*>(part + wv * A.f + c0) = mine;
-    __syncthreads();
-    float2 s = make_float2(0.f, 0.f);
-    if (on) {
-      s = *reinterpret_cast<const float2*>(part + c0);
-#pragma unroll
-      for (int w = 1; w < kAlsWaves; ++w) {
-        const float2 t = *reinterpret_cast<const float2*>(part + w * A.f + c0);
-        s.x += t.x;
-        s.y += t.y;
-      }
-    }
-    __syncthreads();  // part is free again
-    return s;
+  float2 acc = make_float2(0.f, 0.f);
+  row_walk<false>(A.I, b, e, LONG ? wv : 0, LONG ? kRowWaves : 1, lane, c0, on,
+                  [&](float2 y, float cu, float) __attribute__((always_inline)) {
+                    const float d = als_dot(y, v);
+                    const float w = RES ? cu - (cu - 1.f) * d : (cu - 1.f) * d;
+                    acc.x = fmaf(w, y.x, acc.x);
+                    acc.y = fmaf(w, y.y, acc.y);
+                  });
+  if constexpr (LONG) {
+    float none = 0.f;
+    acc = row_wave_order_sum<true, false>(part, A.f, nullptr, lane, wv, c0, on, acc, none);
   }
+  return acc;
 }
 
 template <bool LONG>
@@ -171,7 +109,7 @@ __device__ __forceinline__ void als_row(const AlsArgs& A, int64_t row, const flo
   const bool on = 2 * lane < f;
   const int64_t b = A.ptr[row], e = A.ptr[row + 1];
   float* xr = A.X + row * A.ldx + c0;
-  float2 x = als_ld2(xr, on);
+  float2 x = row_ld2(xr, on);
   const float2 s = als_sum<true, LONG>(A, b, e, lane, wv, c0, on, part, x);
   const float2 g = als_gv(Gs, f, c0, x);
   float2 r = make_float2(on ? s.x - g.x : 0.f, on ? s.y - g.y : 0.f);
@@ -197,36 +135,28 @@ __device__ __forceinline__ void als_row(const AlsArgs& A, int64_t row, const flo
   if (on && (!LONG || wv == 0)) *reinterpret_cast<float2*>(xr) = x;
 }
 
-__global__ __launch_bounds__(64 * kAlsWaves) void als_half_kernel(AlsArgs A, const float* __restrict__ G) {
+__global__ __launch_bounds__(64 * kRowWaves) void als_half_kernel(AlsArgs A, const float* __restrict__ G) {
   extern __shared__ __attribute__((aligned(16))) float als_lds[];
   float* Gs = als_lds;               // [f][f]
-  float* part = als_lds + A.f * A.f;  // [kAlsWaves][f]
+  float* part = als_lds + A.f * A.f;  // [kRowWaves][f]
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  for (int i = tid; i < A.f * A.f / 4; i += 64 * kAlsWaves)
+  for (int i = tid; i < A.f * A.f / 4; i += 64 * kRowWaves)
     reinterpret_cast<float4*>(Gs)[i] = reinterpret_cast<const float4*>(G)[i];
   __syncthreads();
-  const int64_t first = (int64_t)blockIdx.x * (kAlsBlocks * kAlsWaves);
-  const int64_t last = min<int64_t>(A.n_rows, first + kAlsBlocks * kAlsWaves);
-  for (int64_t r0 = first; r0 < last; r0 += kAlsWaves) {
-    const int64_t row = r0 + wv;
-    if (row < A.n_rows && A.ptr[row + 1] - A.ptr[row] <= kAlsLongRow) als_row<false>(A, row, Gs, part, lane, wv);
-    for (int w = 0; w < kAlsWaves; ++w) {  // the block's long rows, by all waves (workgroup-uniform)
-      const int64_t lr = r0 + w;
-      if (lr < A.n_rows && A.ptr[lr + 1] - A.ptr[lr] > kAlsLongRow) als_row<true>(A, lr, Gs, part, lane, wv);
-    }
-  }
+  const int64_t first = (int64_t)blockIdx.x * (kAlsBlocks * kRowWaves);
+  const int64_t last = min<int64_t>(A.n_rows, first + kAlsBlocks * kRowWaves);
+  for (int64_t r0 = first; r0 < last; r0 += kRowWaves)
+    row_block(
+        A.ptr, A.n_rows, r0, wv,
+        [&](int64_t row) __attribute__((always_inline)) { als_row<false>(A, row, Gs, part, lane, wv); },
+        [&](int64_t row) __attribute__((always_inline)) { als_row<true>(A, row, Gs, part, lane, wv); });
 }
 
-int als_rows_per_block() { return kAlsWaves; }
-int als_long_row() { return kAlsLongRow; }
-
-static bool als_table_ok(const float* t, int64_t f, int64_t ld) {
-  return t != nullptr && (reinterpret_cast<uintptr_t>(t) & 15) == 0 && ld >= f && ld % 4 == 0;
-}
+int als_rows_per_block() { return kRowWaves; }
+int als_long_row() { return kRowLong; }
 
 int launch_als_gram(const float* Y, int64_t n, int64_t f, int64_t ld, float reg, float* G, hipStream_t st) {
-  PS_REQUIRE(f >= 4 && f <= kAlsMaxF && f % 4 == 0, kErrArg, "als_gram: need 4 <= f <= 128, f % 4 == 0");
-  PS_REQUIRE(als_table_ok(Y, f, ld), kErrArg, "als_gram: Y must be 16-byte aligned with ld >= f, ld % 4 == 0");
+  PS_TRY(row_tables_ok("als_gram", f, {{"Y", Y, ld}}));
   PS_REQUIRE(G != nullptr && (reinterpret_cast<uintptr_t>(G) & 15) == 0, kErrArg, "als_gram: G must be 16-byte aligned");
   PS_REQUIRE(n >= 0 && n <= INT32_MAX, kErrArg, "als_gram: bad row count");
   PS_REQUIRE(reg > 0.f, kErrArg, "als_gram: reg must be positive");  // false for NaN too
@@ -239,29 +169,26 @@ int launch_als_gram(const float* Y, int64_t n, int64_t f, int64_t ld, float reg,
 int launch_als_half(const int64_t* ptr, const int32_t* idx, const float* val, int64_t n_rows, const float* Y,
                     int64_t n_other, int64_t ldy, float* X, int64_t ldx, int64_t f, const float* G, float alpha,
                     int64_t cg_steps, int* err, hipStream_t st) {
-  PS_REQUIRE(f >= 4 && f <= kAlsMaxF && f % 4 == 0, kErrArg, "als_half: need 4 <= f <= 128, f % 4 == 0");
-  PS_REQUIRE(als_table_ok(Y, f, ldy), kErrArg, "als_half: Y must be 16-byte aligned with ld >= f, ld % 4 == 0");
-  PS_REQUIRE(als_table_ok(X, f, ldx), kErrArg, "als_half: X must be 16-byte aligned with ld >= f, ld % 4 == 0");
+  PS_TRY(row_tables_ok("als_half", f, {{"Y", Y, ldy}, {"X", X, ldx}}));
   PS_REQUIRE(G != nullptr && (reinterpret_cast<uintptr_t>(G) & 15) == 0, kErrArg, "als_half: G must be 16-byte aligned");
   PS_REQUIRE(ptr != nullptr, kErrArg, "als_half: null row pointers");
-  PS_REQUIRE(n_rows >= 0 && n_rows <= INT32_MAX && n_other >= 1 && n_other <= INT32_MAX, kErrArg,
-             "als_half: bad sizes");
+  PS_TRY(row_sizes_ok("als_half", n_rows, n_other));
   PS_REQUIRE(cg_steps >= 0 && cg_steps <= INT32_MAX, kErrArg, "als_half: cg_steps must be >= 0");
   PS_REQUIRE(alpha > 0.f && alpha < INFINITY, kErrArg, "als_half: alpha must be positive and finite");
   if (n_rows == 0 || cg_steps == 0) return kOk;  // zero steps leave X as it is
-  const int lds = (int)((f * f + kAlsWaves * f) * 4);
+  const int lds = (int)((f * f + kRowWaves * f) * 4);
   static int prepared = 0;
   if (!prepared) {
     PS_CHECK_HIP(hipFuncSetAttribute((const void*)als_half_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                     (kAlsMaxF * kAlsMaxF + kAlsWaves * kAlsMaxF) * 4));
+                                     (kRowMaxF * kRowMaxF + kRowWaves * kRowMaxF) * 4));
     prepared = 1;
   }
   // A workgroup per kAlsBlocks blocks of rows, not a resident grid striding over all of them: the
   // dispatcher hands the next workgroup to whichever CU has room, so the one that met a hub row is
   // not left with an equal share of the other rows as well.
-  const int grid = ceil_div(n_rows, kAlsBlocks * kAlsWaves);
-  const AlsArgs A{ptr, idx, val, n_rows, Y, n_other, ldy, X, ldx, (int)f, alpha, (int)cg_steps, err};
-  hipLaunchKernelGGL(als_half_kernel, dim3((unsigned)grid), dim3(64 * kAlsWaves), lds, st, A, G);
+  const int grid = ceil_div(n_rows, kAlsBlocks * kRowWaves);
+  const AlsArgs A{ptr, n_rows, {idx, val, alpha, Y, nullptr, n_other, ldy, err}, X, ldx, (int)f, (int)cg_steps};
+  hipLaunchKernelGGL(als_half_kernel, dim3((unsigned)grid), dim3(64 * kRowWaves), lds, st, A, G);
   PS_CHECK_LAUNCH();
   return kOk;
 }

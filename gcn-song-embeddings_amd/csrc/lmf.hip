@@ -21,25 +21,23 @@
 // Rows are MFMA columns, which never mix; items are summed in one fixed order;
 // nothing depends on the grid.
 //
-// lmf_update_kernel: the sparse part and the AdaGrad step, one wave per row, the
-// workgroup for a long row: als_half_kernel's plan (als.hip).
+// lmf_update_kernel: the sparse part and the AdaGrad step on the row plan of
+// rowplan.h, one wave per row, the workgroup for a long row: the walk also
+// gathers by[i] and carries the scalar sum of w_i, and wave 0 finishes a long row.
 #include <algorithm>
 #include <cmath>
 
 #include "lmf.h"
+#include "rowplan.h"
 
 namespace ps {
 
 using f32x16 = __attribute__((ext_vector_type(16))) float;
 
-constexpr int kLmfMaxF = 128;
-constexpr int kLmfWaves = 4;                    // dense: 32-row slabs per workgroup
-constexpr int kLmfRowBlock = 32 * kLmfWaves;    // dense: rows per workgroup
-constexpr int kLmfTile = 32;                    // dense: items per tile
-constexpr int kLmfStride = kLmfMaxF + 4;        // dense: LDS row stride (floats): 16 rows' 16-byte reads cover 64 banks
-constexpr int kLmfUpWaves = 8;                  // update: waves (= ordinary rows) per workgroup
-constexpr int kLmfUpRows = 8;                   // update: item rows whose loads are in flight per step
-constexpr int kLmfLongRow = 512;                // update: a row above this many items is taken by the workgroup
+constexpr int kLmfWaves = 4;                  // dense: 32-row slabs per workgroup
+constexpr int kLmfRowBlock = 32 * kLmfWaves;  // dense: rows per workgroup
+constexpr int kLmfTile = 32;                  // dense: items per tile
+constexpr int kLmfStride = kRowMaxF + 4;      // dense: LDS row stride (floats): 16 rows' 16-byte reads cover 64 banks
 constexpr float kLmfEps = 1e-6f;
 
 // stable logistic function: e = exp(-|s|) never overflows
@@ -177,12 +175,8 @@ __global__ __launch_bounds__(64 * kLmfWaves, 2) void lmf_dense_kernel(LmfDenseAr
 
 struct LmfUpArgs {
   const int64_t* ptr;
-  const int32_t* idx;
-  const float* val;
   int64_t n_rows;
-  const float* Y;
-  const float* by;
-  int64_t n_other, ldy;
+  RowItems I;
   float* X;
   float* bx;
   int64_t ldx;
@@ -193,57 +187,8 @@ struct LmfUpArgs {
   float* H;
   int64_t ldh;
   float* hb;
-  float alpha, reg, lr;
-  int* err;
+  float reg, lr;
 };
-
-__device__ __forceinline__ float2 lmf_ld2(const float* p, bool on) {
-  return on ? *reinterpret_cast<const float2*>(p) : make_float2(0.f, 0.f);
-}
-
-// sum over the items [b, e) taken in groups of 64 (group g0, g0 + gs, ...) of w_i y_i, and of w_i
-__device__ __forceinline__ float2 lmf_items(const LmfUpArgs& A, int64_t b, int64_t e, int g0, int gs, int lane, int c0,
-                                            bool on, float2 x, float bxu, float& wsum) {
-  float2 acc = make_float2(0.f, 0.f);
-  wsum = 0.f;
-  for (int64_t j0 = b + (int64_t)g0 * 64; j0 < e; j0 += (int64_t)gs * 64) {  // wave-uniform
-    const int m = (int)min<int64_t>(64, e - j0);
-    int id = 0;
-    float c = 0.f, bi = 0.f;
-    if (lane < m) {
-      id = A.idx[j0 + lane];
-      if (id < 0 || id >= A.n_other) {  // callers validate; clamp so that no access strays
-        if (A.err) atomicExch(A.err, 1);
-        id = 0;
-      }
-      c = A.alpha * A.val[j0 + lane];
-      bi = A.by[id];
-    }
-    auto add = [&](float2 y, float cu, float bu) __attribute__((always_inline)) {
-      const float s = (wave_sum(fmaf(x.x, y.x, x.y * y.y)) + bxu) + bu;
-      const float w = cu * lmf_sigmoid(-s);
-      acc.x = fmaf(w, y.x, acc.x);
-      acc.y = fmaf(w, y.y, acc.y);
-      wsum += w;
-    };
-    int u = 0;
-    for (; u + kLmfUpRows <= m; u += kLmfUpRows) {
-      float2 y[kLmfUpRows];
-      float cu[kLmfUpRows], bu[kLmfUpRows];
-#pragma unroll
-      for (int r = 0; r < kLmfUpRows; ++r) {
-        y[r] = lmf_ld2(A.Y + (int64_t)__shfl(id, u + r, 64) * A.ldy + c0, on);
-        cu[r] = __shfl(c, u + r, 64);
-        bu[r] = __shfl(bi, u + r, 64);
-      }
-#pragma unroll
-      for (int r = 0; r < kLmfUpRows; ++r) add(y[r], cu[r], bu[r]);
-    }
-    for (; u < m; ++u)
-      add(lmf_ld2(A.Y + (int64_t)__shfl(id, u, 64) * A.ldy + c0, on), __shfl(c, u, 64), __shfl(bi, u, 64));
-  }
-  return acc;
-}
 
 // LONG: called by every wave of the workgroup; barriers inside.
 template <bool LONG>
@@ -253,33 +198,24 @@ __device__ __forceinline__ void lmf_row(const LmfUpArgs& A, int64_t row, float* 
   const int64_t b = A.ptr[row], e = A.ptr[row + 1];
   float* xr = A.X + row * A.ldx + c0;
   float* hr = A.H + row * A.ldh + c0;
-  const float2 x = lmf_ld2(xr, on);
+  const float2 x = row_ld2(xr, on);
   const float bxu = A.bx[row];
-  float2 s;
-  float ws;
-  if constexpr (!LONG) {
-    s = lmf_items(A, b, e, 0, 1, lane, c0, on, x, bxu, ws);
-  } else {
-    float wmine;
-    const float2 mine = lmf_items(A, b, e, wv, kLmfUpWaves, lane, c0, on, x, bxu, wmine);
-    float* wpart = part + kLmfUpWaves * kLmfMaxF;
-    if (on) *reinterpret_cast<float2*>(part + wv * kLmfMaxF + c0) = mine;
-    if (lane == 0) wpart[wv] = wmine;
-    __syncthreads();
-    if (wv != 0) return;  // wave 0 adds the partial sums in wave order and finishes the row
-    s = make_float2(0.f, 0.f);
-    if (on) s = *reinterpret_cast<const float2*>(part + c0);
-    ws = wpart[0];
-#pragma unroll
-    for (int w = 1; w < kLmfUpWaves; ++w) {
-      if (on) {
-        const float2 t = *reinterpret_cast<const float2*>(part + w * kLmfMaxF + c0);
-        s.x += t.x;
-        s.y += t.y;
-      }
-      ws += wpart[w];
-    }
+  // the sums over the row's items of w_i y_i, and of w_i
+  float2 acc = make_float2(0.f, 0.f);
+  float ws = 0.f;
+  row_walk<true>(A.I, b, e, LONG ? wv : 0, LONG ? kRowWaves : 1, lane, c0, on,
+                 [&](float2 y, float cu, float bu) __attribute__((always_inline)) {
+                   const float s = (wave_sum(fmaf(x.x, y.x, x.y * y.y)) + bxu) + bu;
+                   const float w = cu * lmf_sigmoid(-s);
+                   acc.x = fmaf(w, y.x, acc.x);
+                   acc.y = fmaf(w, y.y, acc.y);
+                   ws += w;
+                 });
+  if constexpr (LONG) {
+    acc = row_wave_order_sum<false, true>(part, kRowMaxF, part + kRowWaves * kRowMaxF, lane, wv, c0, on, acc, ws);
+    if (wv != 0) return;  // wave 0 has the sums and finishes the row
   }
+  const float2 s = acc;
   if (on) {
     const float2 d = *reinterpret_cast<const float2*>(A.D + row * A.ldd + c0);
     float2 hh = *reinterpret_cast<const float2*>(hr);
@@ -299,37 +235,23 @@ __device__ __forceinline__ void lmf_row(const LmfUpArgs& A, int64_t row, float* 
   }
 }
 
-__global__ __launch_bounds__(64 * kLmfUpWaves) void lmf_update_kernel(LmfUpArgs A) {
-  __shared__ __attribute__((aligned(16))) float part[kLmfUpWaves * kLmfMaxF + kLmfUpWaves];
+__global__ __launch_bounds__(64 * kRowWaves) void lmf_update_kernel(LmfUpArgs A) {
+  __shared__ __attribute__((aligned(16))) float part[kRowWaves * kRowMaxF + kRowWaves];
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  const int64_t r0 = (int64_t)blockIdx.x * kLmfUpWaves;
-  const int64_t row = r0 + wv;
-  if (row < A.n_rows && A.ptr[row + 1] - A.ptr[row] <= kLmfLongRow) lmf_row<false>(A, row, part, lane, wv);
-  for (int w = 0; w < kLmfUpWaves; ++w) {  // the block's long rows, by all waves (workgroup-uniform)
-    const int64_t lr = r0 + w;
-    if (lr < A.n_rows && A.ptr[lr + 1] - A.ptr[lr] > kLmfLongRow) {
-      lmf_row<true>(A, lr, part, lane, wv);
-      __syncthreads();  // part is free again
-    }
-  }
+  row_block(
+      A.ptr, A.n_rows, (int64_t)blockIdx.x * kRowWaves, wv,
+      [&](int64_t row) __attribute__((always_inline)) { lmf_row<false>(A, row, part, lane, wv); },
+      [&](int64_t row) __attribute__((always_inline)) { lmf_row<true>(A, row, part, lane, wv); });
 }
 
 int lmf_row_block() { return kLmfRowBlock; }
-int lmf_long_row() { return kLmfLongRow; }
-
-static bool lmf_table_ok(const float* t, int64_t f, int64_t ld) {
-  return t != nullptr && (reinterpret_cast<uintptr_t>(t) & 15) == 0 && ld >= f && ld % 4 == 0;
-}
+int lmf_long_row() { return kRowLong; }
 
 int launch_lmf_dense(const float* X, const float* bx, int64_t n_rows, int64_t ldx, const float* Y, const float* by,
                      int64_t n_other, int64_t ldy, int64_t f, float* D, int64_t ldd, float* dsum, hipStream_t st) {
-  PS_REQUIRE(f >= 4 && f <= kLmfMaxF && f % 4 == 0, kErrArg, "lmf_dense: need 4 <= f <= 128, f % 4 == 0");
-  PS_REQUIRE(lmf_table_ok(X, f, ldx), kErrArg, "lmf_dense: X must be 16-byte aligned with ld >= f, ld % 4 == 0");
-  PS_REQUIRE(lmf_table_ok(Y, f, ldy), kErrArg, "lmf_dense: Y must be 16-byte aligned with ld >= f, ld % 4 == 0");
-  PS_REQUIRE(lmf_table_ok(D, f, ldd), kErrArg, "lmf_dense: D must be 16-byte aligned with ld >= f, ld % 4 == 0");
+  PS_TRY(row_tables_ok("lmf_dense", f, {{"X", X, ldx}, {"Y", Y, ldy}, {"D", D, ldd}}));
   PS_REQUIRE(bx != nullptr && by != nullptr && dsum != nullptr, kErrArg, "lmf_dense: null bias or dsum");
-  PS_REQUIRE(n_rows >= 0 && n_rows <= INT32_MAX && n_other >= 1 && n_other <= INT32_MAX, kErrArg,
-             "lmf_dense: bad sizes");
+  PS_TRY(row_sizes_ok("lmf_dense", n_rows, n_other));
   if (n_rows == 0) return kOk;
   const LmfDenseArgs A{X, bx, n_rows, ldx, Y, by, n_other, ldy, (int)f, D, ldd, dsum};
   const dim3 grid((unsigned)ceil_div(n_rows, kLmfRowBlock)), block(64 * kLmfWaves);
@@ -347,23 +269,17 @@ int launch_lmf_update(const int64_t* ptr, const int32_t* idx, const float* val, 
                       const float* by, int64_t n_other, int64_t ldy, float* X, float* bx, int64_t ldx, int64_t f,
                       const float* D, int64_t ldd, const float* dsum, float* H, int64_t ldh, float* hb, float alpha,
                       float reg, float lr, int* err, hipStream_t st) {
-  PS_REQUIRE(f >= 4 && f <= kLmfMaxF && f % 4 == 0, kErrArg, "lmf_update: need 4 <= f <= 128, f % 4 == 0");
-  PS_REQUIRE(lmf_table_ok(Y, f, ldy), kErrArg, "lmf_update: Y must be 16-byte aligned with ld >= f, ld % 4 == 0");
-  PS_REQUIRE(lmf_table_ok(X, f, ldx), kErrArg, "lmf_update: X must be 16-byte aligned with ld >= f, ld % 4 == 0");
-  PS_REQUIRE(lmf_table_ok(D, f, ldd), kErrArg, "lmf_update: D must be 16-byte aligned with ld >= f, ld % 4 == 0");
-  PS_REQUIRE(lmf_table_ok(H, f, ldh), kErrArg, "lmf_update: H must be 16-byte aligned with ld >= f, ld % 4 == 0");
+  PS_TRY(row_tables_ok("lmf_update", f, {{"Y", Y, ldy}, {"X", X, ldx}, {"D", D, ldd}, {"H", H, ldh}}));
   PS_REQUIRE(ptr != nullptr && by != nullptr && bx != nullptr && dsum != nullptr && hb != nullptr, kErrArg,
              "lmf_update: null row pointers, bias, dsum or hb");
-  PS_REQUIRE(n_rows >= 0 && n_rows <= INT32_MAX && n_other >= 1 && n_other <= INT32_MAX, kErrArg,
-             "lmf_update: bad sizes");
+  PS_TRY(row_sizes_ok("lmf_update", n_rows, n_other));
   PS_REQUIRE(alpha > 0.f && alpha < INFINITY, kErrArg, "lmf_update: alpha must be positive and finite");
   PS_REQUIRE(reg >= 0.f && reg < INFINITY && lr >= 0.f && lr < INFINITY, kErrArg,
              "lmf_update: reg and lr must be non-negative and finite");
   if (n_rows == 0) return kOk;
-  const LmfUpArgs A{ptr, idx, val, n_rows, Y, by, n_other, ldy, X, bx, ldx, (int)f, D, ldd, dsum, H, ldh, hb,
-                    alpha, reg, lr, err};
-  hipLaunchKernelGGL(lmf_update_kernel, dim3((unsigned)ceil_div(n_rows, kLmfUpWaves)), dim3(64 * kLmfUpWaves), 0,
-                     st, A);
+  const LmfUpArgs A{ptr, n_rows, {idx, val, alpha, Y, by, n_other, ldy, err}, X, bx, ldx, (int)f, D, ldd, dsum, H, ldh,
+                    hb, reg, lr};
+  hipLaunchKernelGGL(lmf_update_kernel, dim3((unsigned)ceil_div(n_rows, kRowWaves)), dim3(64 * kRowWaves), 0, st, A);
   PS_CHECK_LAUNCH();
   return kOk;
 }

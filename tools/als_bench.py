@@ -92,12 +92,8 @@ def main():
     X0 = ((torch.rand(nc, f, generator=gen) - 0.5) / f).cuda()
     Y0 = ((torch.rand(n, f, generator=gen) - 0.5) / f).cuda()
     # the two sides: (csr, rows solved, fixed table)
-    ptr, idx, val = ct[:3]
-    rows_u = bl._csr_rows(ptr)
-    order = torch.sort(idx.to(torch.int64), stable=True).indices
-    tr = (bl._csr_ptr(idx.to(torch.int64), n), rows_u[order].to(torch.int32).contiguous(), val[order].contiguous(),
-          n, nc)
-    sides = {"users": (ct, X0, Y0), "items": (tr, Y0, X0)}
+    idx = ct[1]
+    sides = {"users": (ct, X0, Y0), "items": (bl._csr_transpose(*ct), Y0, X0)}
     L, st = nat.lib(), nat.stream_ptr
     err = torch.zeros(1, dtype=torch.int32, device="cuda")
     G = {s: torch.empty((f, f), dtype=torch.float32, device="cuda") for s in sides}

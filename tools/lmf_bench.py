@@ -81,13 +81,9 @@ def main():
     # trained-size biases, so that the scores are not all near 0
     bx0 = (torch.rand(nc, generator=gen) - 0.5).cuda()
     by0 = (torch.rand(n, generator=gen) - 2.5).cuda()
-    ptr, idx, val = ct[:3]
-    rows_u = bl._csr_rows(ptr)
-    order = torch.sort(idx.to(torch.int64), stable=True).indices
-    tr = (bl._csr_ptr(idx.to(torch.int64), n), rows_u[order].to(torch.int32).contiguous(), val[order].contiguous(),
-          n, nc)
+    idx = ct[1]
     # the two sides: (csr, rows updated, their bias, fixed table, its bias)
-    sides = {"users": (ct, X0, bx0, Y0, by0), "items": (tr, Y0, by0, X0, bx0)}
+    sides = {"users": (ct, X0, bx0, Y0, by0), "items": (bl._csr_transpose(*ct), Y0, by0, X0, bx0)}
     L, st = nat.lib(), nat.stream_ptr
     err = torch.zeros(1, dtype=torch.int32, device="cuda")
     D = {s: torch.empty_like(sides[s][1]) for s in sides}
