@@ -30,9 +30,17 @@ factorisation by full-gradient AdaGrad ascent (csrc/lmf.hip: a fused
 sigmoid(X Y^T) Y MFMA kernel and a sparse update), again this package's own
 definition.
 
-The reference's other baseline recommenders (node2vec, implicit's bpr,
-networkx similarities, lib/gnns) are out of scope; their libraries are not
-part of this build.  Names, signatures, return types and RNG consumption
+``FastNode2Vec`` (baselines.py:223-255) stands on ``Node2Vec``: second-order
+(p, q) walks by rejection sampling on the counter-based Philox generator and a
+skip-gram fit with the negatives taken in expectation, a closed objective over
+the walks' window co-occurrence counts that runs on the LMF scaffold
+(csrc/n2v.hip: a walk kernel, the column-weighted form of the fused dense
+kernel and a sparse update).  Again this package's own definition,
+deterministic, with no parity with fastnode2vec or gensim claimed.
+
+The reference's other baseline recommenders (implicit's bpr, networkx
+similarities, lib/gnns) are out of scope; their libraries are not part of this
+build.  Names, signatures, return types and RNG consumption
 follow the reference; compute runs in HIP (no CPU fallback).
 """
 from __future__ import annotations
@@ -598,6 +606,20 @@ def _membership_pairs(g, n_tracks, dev, who):
     return torch.where(s_tr, src, dst)[keep], torch.where(s_tr, dst, src)[keep] - n_tracks
 
 
+def _membership_csrs(g, n_tracks, who):
+    """The two membership CSRs on the GPU, duplicates removed and rows ascending:
+    ((ptr, idx int32) tracks -> collections, (ptr, idx int32) collections ->
+    tracks, n_cols).  Membership is _membership_pairs' rule."""
+    n_cols = len(g) - n_tracks
+    track, col = _membership_pairs(g, n_tracks, nat.device(), who)
+    # one 64-bit key per membership: unique() removes duplicates and sorts the rows
+    tc = torch.unique(track * max(n_cols, 1) + col)
+    ct = torch.unique(col * n_tracks + track)
+    t2c = (_csr_ptr(tc // max(n_cols, 1), n_tracks), (tc % max(n_cols, 1)).to(torch.int32).contiguous())
+    c2t = (_csr_ptr(ct // n_tracks, n_cols), (ct % n_tracks).to(torch.int32).contiguous())
+    return t2c, c2t, n_cols
+
+
 class JaccardFast(PredictionModel):
     """Nearest neighbours by the Jaccard similarity of the tracks' collection
     sets (baselines.py:194-220):  |C(q) & C(t)| / (|C(q) | C(t)| + 1e-10).
@@ -631,18 +653,8 @@ class JaccardFast(PredictionModel):
         nat.require_gpu()
         self.ids = ids
         self.n = n_tracks = len(ids)
-        self.n_cols = n_cols = len(g) - n_tracks
-        track, col = _membership_pairs(g, n_tracks, nat.device(), "JaccardFast")
-        # one 64-bit key per membership: unique() removes duplicates and sorts the rows
-        tc = torch.unique(track * max(n_cols, 1) + col)
-        ct = torch.unique(col * n_tracks + track)
-        self._t2c = self._csr(tc // max(n_cols, 1), tc % max(n_cols, 1), n_tracks)
-        self._c2t = self._csr(ct // n_tracks, ct % n_tracks, n_cols)
+        self._t2c, self._c2t, self.n_cols = _membership_csrs(g, n_tracks, "JaccardFast")
         self.nbh_sizes = self._t2c[0][1:] - self._t2c[0][:-1]  # int64 [n_tracks], on the GPU
-
-    @staticmethod
-    def _csr(rows, cols, n_rows):
-        return _csr_ptr(rows, n_rows), cols.to(torch.int32).contiguous()
 
     def _queries(self, nodeset):
         qs = torch.as_tensor(nodeset).reshape(-1).to(torch.int64)
@@ -1079,6 +1091,327 @@ class ColTrackLMF(_ColTrack, _CfLMF):
     (the reference's algo="lmf"; ``LMF`` above)."""
 
 
+# ----------------------------------------------------------------------------- node2vec
+# baselines.py:223-255.  A graph is the tuple (ptr int64 [n + 1], idx int32,
+# weight int64 or None, n): an undirected CSR, rows ascending, no duplicates, no
+# self loops, positive integer weights (None: unweighted).
+def project_bipartite_graph(g, ids):
+    """The weighted track-track projection of the bipartite graph (the
+    reference's project_bipartite_graph, networkx's weighted_projected_graph):
+    (ptr, idx int32, weight int64, n) on the GPU, n = len(ids), the weight of
+    (a, b) the number of collections that hold both, the diagonal dropped.
+    Membership is JaccardFast.train's rule.  Built from batches of
+    pinsage_cooc_counts rows: no n x n matrix exists at once."""
+    nat.require_gpu()
+    n = len(ids)
+    t2c, c2t, n_cols = _membership_csrs(g, n, "project_bipartite_graph")
+    L = nat.lib()
+    step = _batch_rows(n, n)
+    err = torch.zeros(1, dtype=torch.int32, device="cuda")
+    lens, cols, wts = [], [], []
+    for q0 in range(0, n, step):
+        qd = torch.arange(q0, min(q0 + step, n), dtype=torch.int64, device="cuda")
+        nq = int(qd.numel())
+        out = torch.empty((nq, n), dtype=torch.int32, device="cuda")
+        nat.check(L.pinsage_cooc_counts(nat.ptr(t2c[0]), nat.ptr(t2c[1]), nat.ptr(c2t[0]), nat.ptr(c2t[1]), n, n_cols,
+                                        nat.ptr(qd), nq, nat.ptr(out), nat.ptr(err), nat.stream_ptr()), "cooc_counts")
+        out[torch.arange(nq, device="cuda"), qd] = 0  # the diagonal: a track's own collection count
+        r, c = torch.nonzero(out, as_tuple=True)   # row-major: rows ascending, columns ascending within a row
+        lens.append(torch.bincount(r, minlength=nq))
+        cols.append(c.to(torch.int32))
+        wts.append(out[r, c].to(torch.int64))
+    ptr = torch.zeros(n + 1, dtype=torch.int64, device="cuda")
+    torch.cumsum(torch.cat(lens), 0, out=ptr[1:])
+    return ptr, torch.cat(cols).contiguous(), torch.cat(wts).contiguous(), n
+
+
+def bipartite_graph(g, ids):
+    """The unweighted graph over tracks [0, len(ids)) and collections (the rest
+    of g's nodes), symmetrised: (ptr, idx int32, None, len(g)) on the GPU, one
+    edge each way per membership (JaccardFast.train's rule), however often and
+    in whichever direction g stores it."""
+    nat.require_gpu()
+    n_tracks, n_all = len(ids), len(g)
+    track, col = _membership_pairs(g, n_tracks, nat.device(), "bipartite_graph")
+    col = col + n_tracks
+    key = torch.unique(torch.cat([track * n_all + col, col * n_all + track]))
+    return _csr_ptr(key // n_all, n_all), (key % n_all).to(torch.int32).contiguous(), None, n_all
+
+
+def n2v_cooccurrence(walks, n, context, device=None):
+    """The window co-occurrence counts of walks (int [n_walks, length], -1 past a
+    walk's end): cell (a, b) counts the position pairs i != j of one walk with
+    |i - j| <= context, walk[i] = a, walk[j] = b, both >= 0.  Every pair is
+    counted in both orders, so the matrix is symmetric.  A sparse matrix tuple
+    (ptr, idx int32, val float32, n, n) on ``device`` (default: the walks').
+    Plain torch; the walks are taken in chunks whose keys fit KNN_SCRATCH_BYTES.
+    A count of 2^24 or more is no longer exact in float32 and raises."""
+    w = torch.as_tensor(walks)
+    if w.dim() != 2:
+        raise ValueError(f"n2v_cooccurrence: walks must be [n_walks, length], got {tuple(w.shape)}")
+    n, context = int(n), int(context)
+    if n < 1 or context < 1:
+        raise ValueError(f"n2v_cooccurrence: n = {n}, context = {context}")
+    dev = w.device if device is None else torch.device(device)
+    w = w.to(device=dev, dtype=torch.int64)
+    if w.numel() and int(w.max()) >= n:
+        raise IndexError(f"n2v_cooccurrence: node ids out of range for {n} nodes")
+    n_walks, length = int(w.shape[0]), int(w.shape[1])
+    # per walk 2 * context * length keys of 8 bytes, and unique()'s sort works on copies of them
+    step = max(1, KNN_SCRATCH_BYTES // max(1, 64 * context * length))
+    keys = torch.empty(0, dtype=torch.int64, device=dev)
+    counts = torch.empty(0, dtype=torch.int64, device=dev)
+    for w0 in range(0, n_walks, step):
+        c = w[w0:w0 + step]
+        new = []
+        for d in range(1, min(context, length - 1) + 1):
+            a, b = c[:, :-d], c[:, d:]
+            ok = (a >= 0) & (b >= 0)
+            a, b = a[ok], b[ok]
+            new += [a * n + b, b * n + a]
+        if not new:
+            continue
+        k, cnt = torch.unique(torch.cat(new), return_counts=True)
+        keys, inv = torch.unique(torch.cat([keys, k]), return_inverse=True)
+        counts = torch.zeros(keys.numel(), dtype=torch.int64, device=dev).index_add_(0, inv, torch.cat([counts, cnt]))
+    if counts.numel() and int(counts.max()) >= 1 << 24:
+        raise OverflowError("n2v_cooccurrence: a count reached 2^24 and is not exact in float32")
+    return _csr_ptr(keys // n, n), (keys % n).to(torch.int32).contiguous(), counts.to(torch.float32), n, n
+
+
+def sgns_objective(C, U, V, negative, noise, regularization):
+    """The skip-gram objective with expected negatives (to be maximised)
+
+        L = sum_wc C_wc log sig(u_w.v_c) + K sum_w #(w) sum_c P(c) log sig(-u_w.v_c)
+            - (reg / 2)(|U|^2 + |V|^2),     #(w) = sum_c C_wc,  K = negative,  P = noise,
+
+    in float64 on the tables' device.  The sum over ALL cells runs in row chunks
+    of at most 2^24 cells."""
+    ptr, idx, val = C[:3]
+    U, V = U.to(torch.float64), V.to(torch.float64)
+    dev = U.device
+    ptr, idx, val = ptr.to(dev), idx.to(dev), val.to(device=dev, dtype=torch.float64)
+    P = torch.as_tensor(noise).to(device=dev, dtype=torch.float64)
+    rows = _csr_rows(ptr)
+    n = int(U.shape[0])
+    cnt = torch.zeros(n, dtype=torch.float64, device=dev).index_add_(0, rows, val)
+    step = max(1, _LMF_CELLS // max(1, int(V.shape[0])))
+    total = torch.zeros((), dtype=torch.float64, device=dev)
+    for r0 in range(0, n, step):
+        s = U[r0:r0 + step] @ V.T
+        total = total - float(negative) * (cnt[r0:r0 + step, None] * (_softplus64(s) * P[None, :])).sum()
+    for i in range(0, int(idx.numel()), 1 << 20):
+        r, j = rows[i:i + (1 << 20)], idx[i:i + (1 << 20)].to(torch.int64)
+        total = total - (val[i:i + (1 << 20)] * _softplus64(-(U[r] * V[j]).sum(1))).sum()
+    return float(total - 0.5 * float(regularization) * ((U * U).sum() + (V * V).sum()))
+
+
+N2V_MAX_BIAS_RATIO = 16.0  # the walk kernel's bound on max(1/p, 1, 1/q) / min(1/p, 1, 1/q)
+
+
+class Node2Vec(_RowFit):
+    """node2vec (Grover & Leskovec 2016) on the kernels of csrc/n2v.hip: what the
+    reference takes from fastnode2vec (baselines.py:223-255).  The model is THIS
+    PROJECT'S DEFINITION, deterministic and stated here in full; that package and
+    gensim cannot be run here and no parity with their numbers is claimed.  There
+    is no reduced window, no subsampling of frequent nodes, and the negatives are
+    taken in expectation, not sampled.
+
+    Walks.  The graph is an undirected CSR with positive integer edge weights
+    (or none).  From every node v start ``walks_per_node`` walks of
+    ``walk_length`` nodes; walk rho of node v has generator position rho n + v.
+    Step 1 draws a neighbour by edge weight.  From step 2 on a neighbour x of
+    the current node is drawn with probability proportional to weight * beta,
+    beta = 1/p if x is the previous node, 1 if x is a neighbour of the previous
+    node, 1/q otherwise, by rejection: propose by weight, accept with
+    probability beta / max(1/p, 1, 1/q).  Draws are Philox4x32-10 words keyed by
+    (seed; step * 256 + try, position) and the arithmetic is integer apart from
+    one fp32 compare (pinsage_n2v_walk in include/pinsage_hip.h states it word
+    for word), so the walks depend on (seed, graph) only.  A node without edges
+    ends its walk.  max(1/p, 1, 1/q) / min(1/p, 1, 1/q) may not exceed 16.
+
+    Counts.  C_ab = the number of position pairs i != j of one walk with
+    |i - j| <= ``context`` that hold (a, b): ``n2v_cooccurrence``, symmetric.
+    #(w) = sum_c C_wc;  P(c) = #(c)^ns_exponent / sum, in float64 on the host,
+    rounded to fp32.
+
+    Fit.  Tables U (centre, ``embedding``) and V (``context_factors``), both
+    [n, dim], s_wc = u_w . v_c, no biases, K = ``negative``.  MAXIMISE
+
+        L = sum_wc C_wc log sig(s_wc) + K sum_w #(w) sum_c P(c) log sig(-s_wc)
+            - (reg / 2)(|U|^2 + |V|^2)
+
+    which is the skip-gram objective with each pair's K sampled negatives
+    replaced by their expectation under P.  One iteration updates every centre
+    row from V, then every context row from the new U.  A half-iteration is
+    Jacobi; per row w of X against Y, in fp32, AdaGrad accumulators from zero:
+
+        D   = sum_all c cw_c sig(x_w . y_c) y_c
+        g   = sum_obs C_wc sig(-(x_w . y_c)) y_c - rw_w D - reg x_w
+        h  += g^2 (elementwise);   x_w += lr g / sqrt(1e-6 + h)
+
+    with (cw, rw) = (P, K #) for the centre half and (K #, P) for the context
+    half.  D comes from one fused MFMA kernel (pinsage_sgns_dense: no n x n
+    buffer, O(n^2 dim) work per half-iteration, the scaling limit LMF has), the
+    rest from pinsage_sgns_update.
+
+    Randomness.  The Philox seed is ``random_state`` or, with None, one
+    ``torch.randint(0, 2**63 - 1, (1,))`` from torch's global generator, drawn
+    before the tables.  Initial tables: (torch.rand(n, dim) - 0.5) / dim on the
+    host, U first, then V, from a torch.Generator seeded with ``random_state``
+    or, with None, from the global generator."""
+
+    _who = "Node2Vec"
+
+    def __init__(self, dim=128, walk_length=20, context=10, p=2.0, q=0.5, walks_per_node=10, negative=5,
+                 ns_exponent=0.75, learning_rate=0.1, regularization=0.0, iterations=30, random_state=None):
+        super().__init__(dim, random_state)
+        inf = float("inf")
+        if not (1 <= int(walk_length) < 1 << 24 and int(context) >= 1 and int(walks_per_node) >= 1):
+            raise ValueError("Node2Vec: need 1 <= walk_length < 2^24, context >= 1, walks_per_node >= 1")
+        if not (0 < p < inf and 0 < q < inf):
+            raise ValueError("Node2Vec: p and q must be positive and finite")
+        betas = (1.0 / p, 1.0, 1.0 / q)
+        if max(betas) / min(betas) > N2V_MAX_BIAS_RATIO:
+            raise ValueError(f"Node2Vec: max(1/p, 1, 1/q) / min(1/p, 1, 1/q) above {N2V_MAX_BIAS_RATIO:g}")
+        if not (0 < negative < inf and 0 <= ns_exponent < inf and 0 <= learning_rate < inf
+                and 0 <= regularization < inf and int(iterations) >= 0):
+            raise ValueError("Node2Vec: need finite negative > 0, ns_exponent >= 0, learning_rate >= 0, "
+                             "regularization >= 0, iterations >= 0")
+        self.dim = self.factors
+        self.walk_length, self.context, self.walks_per_node = int(walk_length), int(context), int(walks_per_node)
+        self.p, self.q, self.negative, self.ns_exponent = float(p), float(q), float(negative), float(ns_exponent)
+        self.learning_rate, self.regularization = float(learning_rate), float(regularization)
+        self.iterations = int(iterations)
+        self.embedding = self.context_factors = self.cooccurrence = self.noise = self.walks = None
+
+    def _graph(self, graph_csr):
+        ptr, idx, weight, n = graph_csr
+        n = int(n)
+        ptr = torch.as_tensor(ptr).to(device="cuda", dtype=torch.int64).contiguous()
+        idx = torch.as_tensor(idx).to(device="cuda", dtype=torch.int32).contiguous()
+        if n < 1 or int(ptr.numel()) != n + 1 or int(ptr[0]) != 0 or int(ptr[-1]) != int(idx.numel()) \
+                or bool((ptr[1:] < ptr[:-1]).any()):
+            raise ValueError("Node2Vec: the CSR arrays do not fit together")
+        if idx.numel() and (int(idx.min()) < 0 or int(idx.max()) >= n):
+            raise IndexError(f"Node2Vec: neighbour ids out of range for {n} nodes")
+        cum = None
+        if weight is not None:
+            wt = torch.as_tensor(weight).to(device="cuda", dtype=torch.int64)
+            if int(wt.numel()) != int(idx.numel()) or (wt.numel() and int(wt.min()) < 1):
+                raise ValueError("Node2Vec: weights must be positive integers, one per edge")
+            run = torch.cumsum(wt, 0)
+            before = torch.cat([torch.zeros(1, dtype=torch.int64, device="cuda"), run])[ptr[:-1]]
+            cum = (run - torch.repeat_interleave(before, ptr[1:] - ptr[:-1])).contiguous()
+        return ptr, idx, cum, n
+
+    def sample_walks(self, graph_csr, seed):
+        """int32 [walks_per_node * n, walk_length] on the GPU: row rho n + v is walk
+        rho of node v (pinsage_n2v_walk; -1 past a walk's end)."""
+        nat.require_gpu()
+        ptr, idx, cum, n = self._graph(graph_csr)
+        starts = torch.arange(n, dtype=torch.int64, device="cuda").repeat(self.walks_per_node)
+        walks = torch.empty((self.walks_per_node * n, self.walk_length), dtype=torch.int32, device="cuda")
+        err = torch.zeros(1, dtype=torch.int32, device="cuda")
+        nat.check(nat.lib().pinsage_n2v_walk(nat.ptr(ptr), nat.ptr(idx), nat.ptr(cum), n, nat.ptr(starts),
+                                             int(starts.numel()), self.walk_length, 1.0 / self.p, 1.0 / self.q,
+                                             int(seed), 0, 0, nat.ptr(walks), nat.ptr(err), nat.stream_ptr()),
+                  "n2v_walk")
+        if int(err):
+            raise IndexError(f"Node2Vec: node ids out of range for {n} nodes")
+        return walks
+
+    def _half(self, C, cw, rw, Y, X, H, D, err):
+        ptr, idx, val, n = C[:4]
+        L, f = nat.lib(), self.factors
+        nat.check(L.pinsage_sgns_dense(nat.ptr(X), n, f, nat.ptr(Y), nat.ptr(cw), n, f, f, nat.ptr(D), f,
+                                       nat.stream_ptr()), "sgns_dense")
+        nat.check(L.pinsage_sgns_update(nat.ptr(ptr), nat.ptr(idx), nat.ptr(val), nat.ptr(rw), n, nat.ptr(Y), n, f,
+                                        nat.ptr(X), f, f, nat.ptr(D), f, nat.ptr(H), f, self.regularization,
+                                        self.learning_rate, nat.ptr(err), nat.stream_ptr()), "sgns_update")
+
+    def fit(self, graph_csr, callback=None, cooccurrence=None, embedding=None, context_factors=None):
+        """graph_csr: (ptr, idx, weight or None, n).  Sets ``embedding`` (U),
+        ``context_factors`` (V), ``cooccurrence`` (C), ``noise`` (P) and
+        ``walks``.  ``callback(iteration, self)`` runs after every iteration, the
+        tables set (monitoring).  With ``cooccurrence`` (a matrix tuple as
+        n2v_cooccurrence returns) no walk is sampled and graph_csr may be None;
+        given tables are copied, not written."""
+        nat.require_gpu()
+        if self.random_state is None:
+            seed = int(torch.randint(0, 2 ** 63 - 1, (1,)))
+        else:
+            seed = int(self.random_state) & (2 ** 64 - 1)
+        if cooccurrence is None:
+            self.walks = self.sample_walks(graph_csr, seed)
+            n = int(graph_csr[3])
+            C = n2v_cooccurrence(self.walks, n, self.context)
+        else:
+            ptr, idx, val, n = cooccurrence[:4]
+            n = int(n)
+            C = (torch.as_tensor(ptr).to(device="cuda", dtype=torch.int64).contiguous(),
+                 torch.as_tensor(idx).to(device="cuda", dtype=torch.int32).contiguous(),
+                 torch.as_tensor(val).to(device="cuda", dtype=torch.float32).contiguous(), n, n)
+            if int(C[0].numel()) != n + 1 or int(C[1].numel()) != int(C[2].numel()):
+                raise ValueError("Node2Vec: the CSR arrays do not fit together")
+        cnt = torch.zeros(n, dtype=torch.float64, device="cuda").index_add_(0, _csr_rows(C[0]), C[2].double()).cpu()
+        if not float(cnt.sum()) > 0:
+            raise ValueError("Node2Vec: the walks hold no pair (a graph without edges, or walk_length 1)")
+        import numpy as np
+        c64 = cnt.numpy()
+        pw = np.where(c64 > 0, c64 ** self.ns_exponent, 0.0)  # a node that never occurs has no noise mass
+        P = torch.from_numpy((pw / pw.sum()).astype(np.float32)).cuda()
+        KN = (self.negative * cnt).to(torch.float32).cuda()
+        gen = None if self.random_state is None else torch.Generator().manual_seed(int(self.random_state))
+        U = self._table(embedding, n, gen)
+        V = self._table(context_factors, n, gen)
+        Hu, Hv = torch.zeros_like(U), torch.zeros_like(V)
+        D = torch.empty((n, self.factors), dtype=torch.float32, device="cuda")
+        err = torch.zeros(1, dtype=torch.int32, device="cuda")
+        self.cooccurrence, self.noise = C, P
+        for it in range(self.iterations):
+            self._half(C, P, KN, V, U, Hu, D, err)
+            if it == 0 and int(err):
+                raise IndexError(f"Node2Vec: co-occurrence ids out of range for {n} nodes")
+            self._half(C, KN, P, U, V, Hv, D, err)
+            if callback is not None:
+                self.embedding, self.context_factors = U, V
+                callback(it, self)
+        self.embedding, self.context_factors = U, V
+        self.user_factors, self.item_factors = V, U  # similar_items: over the embedding
+        return self
+
+    def objective(self):
+        """sgns_objective of the fitted tables (a Python float; monitoring and tests)."""
+        return sgns_objective(self.cooccurrence, self.embedding, self.context_factors, self.negative, self.noise,
+                              self.regularization)
+
+
+class FastNode2Vec(EmbeddingModel):
+    """node2vec embeddings of the tracks (baselines.py:223-255): ``Node2Vec`` with
+    the reference's dim 128, walk_length 20, context 10, p 2.0, q 0.5, its
+    epochs = 10 as walks_per_node = 10, on the weighted track-track projection
+    (``projected``) or on the unweighted bipartite graph.  ``embedding`` is the
+    first len(ids) rows of the centre table, a CPU tensor as in the reference."""
+
+    def __init__(self, projected=True):
+        self.model = None
+        self.embedding = None
+        self.projected = projected
+
+    def train(self, g, ids, train_set, test_set, features):
+        graph_csr = project_bipartite_graph(g, ids) if self.projected else bipartite_graph(g, ids)
+        self.model = Node2Vec(dim=128, walk_length=20, context=10, p=2.0, q=0.5, walks_per_node=10)
+        self.model.fit(graph_csr)
+        self.embedding = self.model.embedding[:len(ids)].cpu()
+
+    def embed(self, nodeset):
+        return self.embedding[torch.as_tensor(nodeset).cpu(), :]
+
+    def knn(self, nodeset, k):
+        return knn_from_emb(self.embedding, nodeset, k)
+
+
 class Random(PredictionModel):
     """Random recommendations (baselines.py:380-397): per query the first k of
     a ``torch.randperm(n)`` from torch's global generator, weights of ones (int64,
@@ -1149,4 +1482,5 @@ __all__ = ["PRECOMP_K", "PredictionModel", "EmbeddingModel", "cosine_sim_ab", "k
            "JaccardFast", "Random", "low_co_accuracy", "low_co_accuracy_from_ranks", "LazyKnnDict",
            "compute_results_table", "ALS_MAX_FACTORS", "ALS", "als_loss", "to_col_track_matrix",
            "to_track_track_matrix", "ColTrackCF", "TrackTrackCF", "LMF_MAX_FACTORS", "LMF", "lmf_objective",
-           "ColTrackLMF", "TrackTrackLMF"]
+           "ColTrackLMF", "TrackTrackLMF", "project_bipartite_graph", "bipartite_graph", "n2v_cooccurrence",
+           "sgns_objective", "N2V_MAX_BIAS_RATIO", "Node2Vec", "FastNode2Vec"]

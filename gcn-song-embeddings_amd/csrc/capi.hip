@@ -11,6 +11,7 @@
 #include "aggw.h"
 #include "als.h"
 #include "lmf.h"
+#include "n2v.h"
 #include "capi.h"
 #include "conv.h"
 #include "cooc.h"
@@ -787,6 +788,25 @@ int pinsage_lmf_update(const int64_t* ptr, const int32_t* idx, const float* val,
                        float alpha, float reg, float lr, int* err, void* stream) {
   return launch_lmf_update(ptr, idx, val, n_rows, Y, by, n_other, ldy, X, bx, ldx, f, D, ldd, dsum, H, ldh, hb,
                            alpha, reg, lr, err, (hipStream_t)stream);
+}
+
+int pinsage_n2v_walk(const int64_t* ptr, const int32_t* idx, const int64_t* cum, int64_t n_nodes,
+                     const int64_t* starts, int64_t n_walks, int64_t length, float inv_p, float inv_q, uint64_t seed,
+                     uint32_t offset, int64_t walk_base, int32_t* walks, int* err, void* stream) {
+  return launch_n2v_walk(ptr, idx, cum, n_nodes, starts, n_walks, length, inv_p, inv_q, seed, offset, walk_base, walks,
+                         err, (hipStream_t)stream);
+}
+
+int pinsage_sgns_dense(const float* X, int64_t n_rows, int64_t ldx, const float* Y, const float* cw, int64_t n_other,
+                       int64_t ldy, int64_t f, float* D, int64_t ldd, void* stream) {
+  return launch_sgns_dense(X, n_rows, ldx, Y, cw, n_other, ldy, f, D, ldd, (hipStream_t)stream);
+}
+
+int pinsage_sgns_update(const int64_t* ptr, const int32_t* idx, const float* val, const float* rw, int64_t n_rows,
+                        const float* Y, int64_t n_other, int64_t ldy, float* X, int64_t ldx, int64_t f, const float* D,
+                        int64_t ldd, float* H, int64_t ldh, float reg, float lr, int* err, void* stream) {
+  return launch_sgns_update(ptr, idx, val, rw, n_rows, Y, n_other, ldy, X, ldx, f, D, ldd, H, ldh, reg, lr, err,
+                            (hipStream_t)stream);
 }
 
 int64_t pinsage_knn_scratch_bytes(int64_t n, int64_t batch_rows) {

@@ -25,25 +25,9 @@
 // at an odd stride so the 64 lanes' heaps sit in distinct banks.  The outputs
 // are written cooperatively (one source at a time, coalesced).
 #include "ppr_topk.h"
+#include "philox.h"
 
 namespace ps {
-
-__device__ __forceinline__ uint4 philox10_(uint64_t key, uint4 c) {
-  uint32_t k0 = (uint32_t)key, k1 = (uint32_t)(key >> 32);
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    uint64_t p0 = (uint64_t)0xD2511F53u * c.x;
-    uint64_t p1 = (uint64_t)0xCD9E8D57u * c.z;
-    uint32_t n0 = (uint32_t)(p1 >> 32) ^ c.y ^ k0;
-    uint32_t n2 = (uint32_t)(p0 >> 32) ^ c.w ^ k1;
-    c = make_uint4(n0, (uint32_t)p1, n2, (uint32_t)p0);
-    if (r < 9) {
-      k0 += 0x9E3779B9u;
-      k1 += 0xBB67AE85u;
-    }
-  }
-  return c;
-}
 
 // One source's walk (one wave, LDS keys[2P]): source index s (its runs' slot),
 // graph node src, Philox key seed and stream position pos (kMT: raw words).
@@ -69,7 +53,7 @@ __device__ __forceinline__ void walk_runs_body(
         r1 = rw[3 * j + 1];
         r2 = rw[3 * j + 2];
       } else {
-        const uint4 r = philox10_(seed, make_uint4((uint32_t)j, (uint32_t)pos, (uint32_t)(pos >> 32), offset));
+        const uint4 r = philox10(seed, make_uint4((uint32_t)j, (uint32_t)pos, (uint32_t)(pos >> 32), offset));
         r0 = r.x;
         r1 = r.y;
         r2 = r.z;

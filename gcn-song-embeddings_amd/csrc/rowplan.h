@@ -1,4 +1,4 @@
-// The row plan of the row-wise fits (als.hip, lmf.hip): a workgroup of kRowWaves
+// The row plan of the row-wise fits (als.hip, lmf.hip, n2v.hip): a workgroup of kRowWaves
 // waves owns a block of kRowWaves consecutive CSR rows.  A lane owns columns
 // 2 lane and 2 lane + 1 of every f-vector, so a gathered row of Y is one 8-byte
 // load per lane.  An ordinary row (at most kRowLong items) is one wave's, its

@@ -13,6 +13,7 @@
 // (seed; hop, source position, offset) with a bit-exact CPU twin in oracle/.
 #include "sampler.h"
 #include "mt19937.h"
+#include "philox.h"
 
 namespace ps {
 
@@ -78,24 +79,6 @@ __global__ __launch_bounds__(256) void mt_expand_kernel(const MTChunk* __restric
     avail -= take;
     __syncthreads();
   }
-}
-
-// ---------------------------------------------------------------- Philox4x32-10
-__device__ __forceinline__ uint4 philox10(uint64_t key, uint4 c) {
-  uint32_t k0 = (uint32_t)key, k1 = (uint32_t)(key >> 32);
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    uint64_t p0 = (uint64_t)0xD2511F53u * c.x;
-    uint64_t p1 = (uint64_t)0xCD9E8D57u * c.z;
-    uint32_t n0 = (uint32_t)(p1 >> 32) ^ c.y ^ k0;
-    uint32_t n2 = (uint32_t)(p0 >> 32) ^ c.w ^ k1;
-    c = make_uint4(n0, (uint32_t)p1, n2, (uint32_t)p0);
-    if (r < 9) {
-      k0 += 0x9E3779B9u;
-      k1 += 0xBB67AE85u;
-    }
-  }
-  return c;
 }
 
 // ---------------------------------------------------------------- walk

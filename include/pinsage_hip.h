@@ -907,6 +907,87 @@ int pinsage_lmf_update(const int64_t* ptr, const int32_t* idx, const float* val,
                        const float* D, int64_t ldd, const float* dsum, float* H, int64_t ldh, float* hb,
                        float alpha, float reg, float lr, int* err, void* stream);
 
+/* ------------------------------------------------------------------ node2vec
+ * Grover & Leskovec, "node2vec" (2016), as this project defines it: second-order
+ * (p, q) walks by rejection sampling on a counter-based generator, and skip-gram
+ * with negative sampling fitted on the EXPECTED negatives, a closed objective
+ * over the window co-occurrence counts of the walks.  Deterministic; parity with
+ * fastnode2vec or gensim is not claimed.
+ *
+ * pinsage_n2v_walk.  The graph is an undirected CSR: ptr int64 [n_nodes + 1],
+ * idx int32 ascending within a row, no duplicates, no self loops; cum int64
+ * [nnz] holds per row the inclusive prefix sum of positive integer edge weights
+ * (null: unweighted).  walks is int32 [n_walks][length], walk k in row k,
+ * position 0 its start starts[k]; positions after the walk's end are -1.  Walk
+ * k's generator position is pos = walk_base + k.  Step j >= 1, try t = 0, 1, ..:
+ *   (r0, r1, r2, r3) = Philox4x32-10(key = seed, ctr = (j * 256 + t, pos lo, pos hi, offset))
+ *   total = the current row's last cum (its degree when unweighted)
+ *   pick  = ((r0 | r1 << 32) * total) >> 64
+ *   candidate = the first edge of the row whose cum exceeds pick (idx[row start +
+ *               pick] when unweighted)
+ *   step 1 takes try 0's candidate.  From step 2 on
+ *     beta = inv_p if the candidate is the previous node, 1 if it is a neighbour
+ *            of the previous node, inv_q otherwise;  M = max(inv_p, 1, inv_q)
+ *     accept iff (float)(r2 >> 8) * 0x1p-24f * M < beta
+ *   (the first product is exact: one fp32 multiply and one compare); after 256
+ *   rejected tries the last candidate is taken.
+ * The accepted next node has probability proportional to weight * beta.  With
+ * M / min(beta) <= 16 a try is accepted with probability >= 1/16, so the cap of
+ * 256 tries distorts at most (15/16)^256 ~ 7e-8 of the steps.  A node without
+ * edges ends the walk.  One lane per walk; a walk reads (seed, offset, pos, its
+ * start, the graph) only: the result depends neither on the grid nor on how
+ * walks are batched into calls.  A start or neighbour id outside [0, n_nodes)
+ * sets *err (device, nullable) and is clamped to 0.  Refused (PINSAGE_ERR_ARG,
+ * nothing launched, outputs untouched): inv_p or inv_q not finite or not
+ * positive; max(inv_p, 1, inv_q) / min(inv_p, 1, inv_q) > 16; length < 1 or
+ * >= 2^24; n_nodes < 1 or > INT32_MAX; n_walks < 0 or > INT32_MAX; walk_base < 0;
+ * a null ptr or idx; a null starts or walks unless n_walks == 0, which launches
+ * nothing.
+ *
+ * Skip-gram with expected negatives.  C [n, n] is the symmetric CSR of window
+ * co-occurrence counts, #(w) = sum_c C_wc, P(c) proportional to #(c)^0.75, tables
+ * U (centre) and V (context), s_wc = u_w . v_c, no biases.  The objective to
+ * MAXIMISE is
+ *   L = sum_wc C_wc log sig(s_wc) + K sum_w #(w) sum_c P(c) log sig(-s_wc)
+ *       - (reg / 2)(|U|^2 + |V|^2)
+ * One iteration updates every centre row from V, then every context row from
+ * the new U; a half-iteration is Jacobi with AdaGrad accumulators from zero.
+ * Per row u of X against all of Y, column weight cw, row weight rw, in fp32:
+ *   D[u] = sum_all i cw_i sig(x_u . y_i) y_i
+ *   g    = sum_obs val_i sig(-(x_u . y_i)) y_i - rw_u D[u] - reg x_u
+ *   h   += g^2;   x_u += lr g / sqrt(1e-6 + h)
+ * Centre half: X = U, Y = V, cw = P, rw = K #(w).  Context half: X = V, Y = U,
+ * cw = K #(w), rw = P(c).  sig as for logistic MF above.
+ *
+ * pinsage_sgns_dense: D f32 [n_rows][ldd] for every row of X against all of Y f32
+ * [n_other][ldy], cw f32 [n_other]: pinsage_lmf_dense's fused kernel with
+ * p = cw_i * sig(s) and no row sums.  Exact-f32 MFMA, scores in registers only,
+ * items in ascending order, no atomics: the bits of row u depend on x_u, Y and
+ * cw only.  Columns [f, ld) are neither read nor written.
+ *
+ * pinsage_sgns_update: the rest, in place on X and H f32 [n_rows][ldh], from D of
+ * the old X; CSR as pinsage_als_half with val f32 > 0, rw f32 [n_rows].  In this
+ * order:  s_i = the wave's sum of fma(x.x, y.x, x.y * y.y) (two columns per lane);
+ * w_i = val_i * sig(-s_i);  a = fma(w_i, y_i, a) in CSR order from 0;
+ * g = fma(-reg, x, fma(-rw_u, D[u], a));  h = fma(g, g, h);
+ * x = x + lr * g / sqrt(1e-6 + h).  Row forms as pinsage_lmf_update.  lr == 0
+ * leaves X bit for bit and still updates H.  A row without items and with
+ * rw_u = 0, reg = 0 keeps x exactly (the step is 0 / sqrt(1e-6 + h)).
+ *
+ * All pointers are device memory.  err (nullable): as pinsage_als_half.  Refusals
+ * (PINSAGE_ERR_ARG, nothing launched, outputs untouched) as the logistic MF
+ * pair: f, leading dimensions, alignment, null tables, a null cw, ptr or rw,
+ * reg < 0, lr < 0 or either not finite, a count above INT32_MAX, n_other < 1.
+ * n_rows == 0 is accepted and launches nothing. */
+int pinsage_n2v_walk(const int64_t* ptr, const int32_t* idx, const int64_t* cum, int64_t n_nodes,
+                     const int64_t* starts, int64_t n_walks, int64_t length, float inv_p, float inv_q, uint64_t seed,
+                     uint32_t offset, int64_t walk_base, int32_t* walks, int* err, void* stream);
+int pinsage_sgns_dense(const float* X, int64_t n_rows, int64_t ldx, const float* Y, const float* cw, int64_t n_other,
+                       int64_t ldy, int64_t f, float* D, int64_t ldd, void* stream);
+int pinsage_sgns_update(const int64_t* ptr, const int32_t* idx, const float* val, const float* rw, int64_t n_rows,
+                        const float* Y, int64_t n_other, int64_t ldy, float* X, int64_t ldx, int64_t f, const float* D,
+                        int64_t ldd, float* H, int64_t ldh, float reg, float lr, int* err, void* stream);
+
 /* ------------------------------------------------------------------ train-step engine
  * PinSageModel.forward / PinSage.train_batch (pinsage_model.py:246-265,
  * pinsage_training.py:181-214) with device-resident sizes.  Parameters live in
