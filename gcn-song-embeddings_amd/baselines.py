@@ -755,9 +755,31 @@ def _csr_transpose(ptr, idx, val, n_rows, n_cols):
             n_cols, n_rows)
 
 
+_LMF_CELLS = 1 << 24  # dense cells of lmf_objective and sgns_objective formed at once
+
+
+def _add_observed(total, ptr, idx, X, Y, term):
+    """total + term(x.y, rows, columns, slice) over the stored cells, 2^20 of them at a time, in order."""
+    rows = _csr_rows(ptr)
+    for i in range(0, int(idx.numel()), 1 << 20):
+        sl = slice(i, i + (1 << 20))
+        r, j = rows[sl], idx[sl].to(torch.int64)
+        total = total + term((X[r] * Y[j]).sum(1), r, j, sl)
+    return total
+
+
+def _sub_all_cells(total, X, Y, term):
+    """total - term(X[rows] Y^T, rows) over ALL cells in row chunks of at most _LMF_CELLS cells, in order."""
+    step = max(1, _LMF_CELLS // max(1, int(Y.shape[0])))
+    for r0 in range(0, int(X.shape[0]), step):
+        total = total - term(X[r0:r0 + step] @ Y.T, slice(r0, r0 + step))
+    return total
+
+
 class _RowFit:
-    """What ALS and LMF share: the factor tables, the intake of the matrix and
-    similar_items.  ``_who`` prefixes the error texts."""
+    """What ALS, LMF and Node2Vec share: the factor tables, the intake of the
+    matrix, the iteration loop and similar_items.  ``_who`` prefixes the error
+    texts."""
 
     def __init__(self, factors, random_state):
         if not (4 <= int(factors) <= ALS_MAX_FACTORS and int(factors) % 4 == 0):
@@ -774,32 +796,52 @@ class _RowFit:
             raise ValueError(f"{self._who}: factors of shape {tuple(t.shape)}, expected {(n, f)}")
         return t.to(device="cuda", dtype=torch.float32, copy=True).contiguous()
 
+    def _csr_arrays(self, ptr, idx, val, n_rows):
+        """The three arrays of a CSR on the GPU, checked to fit together."""
+        ptr = torch.as_tensor(ptr).to(device="cuda", dtype=torch.int64).contiguous()
+        idx = torch.as_tensor(idx).to(device="cuda", dtype=torch.int32).contiguous()
+        val = torch.as_tensor(val).to(device="cuda", dtype=torch.float32).contiguous()
+        if int(ptr.numel()) != n_rows + 1 or int(idx.numel()) != int(val.numel()):
+            raise ValueError(f"{self._who}: the CSR arrays do not fit together")
+        return ptr, idx, val
+
+    def _tables(self, first, second, n_first, n_second):
+        """The two factor tables, drawn in this order, and the zeroed device word
+        that a half-iteration sets on a column id out of range."""
+        gen = None if self.random_state is None else torch.Generator().manual_seed(int(self.random_state))
+        return (self._table(first, n_first, gen), self._table(second, n_second, gen),
+                torch.zeros(1, dtype=torch.int32, device="cuda"))
+
     def _intake(self, user_items, user_factors, item_factors):
-        """(R, R^T, X, Y, err): the checked CSR on the GPU and its transpose, the
-        two factor tables (drawn users first, then items) and the zeroed device
-        word that a half-iteration sets on a column id out of range."""
+        """(R, R^T, X, Y, err): the checked CSR on the GPU and its transpose, and
+        what _tables returns, users first."""
         nat.require_gpu()
         ptr, idx, val, n_users, n_items = user_items
         n_users, n_items = int(n_users), int(n_items)
         if n_users < 1 or n_items < 1:
             raise ValueError(f"{self._who}: a {n_users} x {n_items} matrix")
-        ptr = torch.as_tensor(ptr).to(device="cuda", dtype=torch.int64).contiguous()
-        idx = torch.as_tensor(idx).to(device="cuda", dtype=torch.int32).contiguous()
-        val = torch.as_tensor(val).to(device="cuda", dtype=torch.float32).contiguous()
-        if int(ptr.numel()) != n_users + 1 or int(idx.numel()) != int(val.numel()):
-            raise ValueError(f"{self._who}: the CSR arrays do not fit together")
+        ptr, idx, val = self._csr_arrays(ptr, idx, val, n_users)
         if not bool((torch.isfinite(val) & (val > 0)).all()):
             raise ValueError(f"{self._who}: values must be finite and > 0")
         self._user_items = csr_u = (ptr, idx, val, n_users, n_items)
-        gen = None if self.random_state is None else torch.Generator().manual_seed(int(self.random_state))
-        X = self._table(user_factors, n_users, gen)
-        Y = self._table(item_factors, n_items, gen)
-        return csr_u, _csr_transpose(*csr_u), X, Y, torch.zeros(1, dtype=torch.int32, device="cuda")
+        return (csr_u, _csr_transpose(*csr_u)) + self._tables(user_factors, item_factors, n_users, n_items)
 
-    def _ids_checked(self, err):
-        """After the first user half: it has met every column id."""
-        if int(err):
-            raise IndexError(f"{self._who}: item ids out of range for {self._user_items[4]} items")
+    def _iterate(self, first_half, second_half, err, tables, callback=None, bad_ids=None):
+        """``iterations`` times first_half() then second_half(); the error word is
+        read after the first first_half(), which has met every column id.
+        ``tables`` (attribute name -> tensor) are set before every
+        ``callback(iteration, self)`` and at the end."""
+        for it in range(self.iterations):
+            first_half()
+            if it == 0 and int(err):
+                raise IndexError(f"{self._who}: "
+                                 + (bad_ids or f"item ids out of range for {self._user_items[4]} items"))
+            second_half()
+            if callback is not None:
+                vars(self).update(tables)
+                callback(it, self)
+        vars(self).update(tables)
+        return self
 
     def similar_items(self, ids, N=10):
         """(ids int64 [nq, N], scores float32 [nq, N]): the N items nearest to each
@@ -818,12 +860,8 @@ def als_loss(user_items, user_factors, item_factors, regularization, alpha=1.0):
     ptr, idx, val = user_items[:3]
     X, Y = user_factors.to(torch.float64), item_factors.to(torch.float64)
     ptr, idx, val = ptr.to(X.device), idx.to(X.device), val.to(X.device)
-    total = ((X.T @ X) * (Y.T @ Y)).sum()
-    rows = _csr_rows(ptr)
-    for i in range(0, int(idx.numel()), 1 << 20):
-        s = (X[rows[i:i + (1 << 20)]] * Y[idx[i:i + (1 << 20)].to(torch.int64)]).sum(1)
-        c = float(alpha) * val[i:i + (1 << 20)].to(torch.float64)
-        total = total + (c * (1 - s) ** 2 - s * s).sum()
+    total = _add_observed(((X.T @ X) * (Y.T @ Y)).sum(), ptr, idx, X, Y, lambda s, r, j, sl:
+                          (float(alpha) * val[sl].to(torch.float64) * (1 - s) ** 2 - s * s).sum())
     return float(total + float(regularization) * ((X * X).sum() + (Y * Y).sum()))
 
 
@@ -881,20 +919,12 @@ class ALS(_RowFit):
         factor tables are copied, not written."""
         csr_u, csr_i, X, Y, err = self._intake(user_items, user_factors, item_factors)
         G = torch.empty((self.factors, self.factors), dtype=torch.float32, device="cuda")
-        for it in range(self.iterations):
-            self._half(csr_u, Y, X, G, err)
-            if it == 0:
-                self._ids_checked(err)
-            self._half(csr_i, X, Y, G, err)
-        self.user_factors, self.item_factors = X, Y
-        return self
+        return self._iterate(lambda: self._half(csr_u, Y, X, G, err), lambda: self._half(csr_i, X, Y, G, err), err,
+                             {"user_factors": X, "item_factors": Y})
 
     def loss(self):
         """als_loss of the fitted factors (a Python float; monitoring and tests)."""
         return als_loss(self._user_items, self.user_factors, self.item_factors, self.regularization, self.alpha)
-
-
-_LMF_CELLS = 1 << 24  # dense cells of lmf_objective formed at once
 
 
 def _softplus64(s):
@@ -914,18 +944,14 @@ def lmf_objective(user_items, user_factors, item_factors, user_bias, item_bias, 
     bx = torch.as_tensor(user_bias).to(device=X.device, dtype=torch.float64)
     by = torch.as_tensor(item_bias).to(device=X.device, dtype=torch.float64)
     ptr, idx, val = ptr.to(X.device), idx.to(X.device), val.to(X.device)
-    n_items = int(Y.shape[0])
-    step = max(1, _LMF_CELLS // max(1, n_items))
-    total = torch.zeros((), dtype=torch.float64, device=X.device)
-    for r0 in range(0, int(X.shape[0]), step):
-        s = X[r0:r0 + step] @ Y.T + bx[r0:r0 + step, None] + by[None, :]
-        total = total - _softplus64(s).sum()
-    rows = _csr_rows(ptr)
-    for i in range(0, int(idx.numel()), 1 << 20):
-        r, j = rows[i:i + (1 << 20)], idx[i:i + (1 << 20)].to(torch.int64)
-        s = (X[r] * Y[j]).sum(1) + bx[r] + by[j]
-        c = float(alpha) * val[i:i + (1 << 20)].to(torch.float64)
-        total = total + (c * (s - _softplus64(s))).sum()
+
+    def observed(s, r, j, sl):
+        s = s + bx[r] + by[j]
+        return (float(alpha) * val[sl].to(torch.float64) * (s - _softplus64(s))).sum()
+
+    total = _sub_all_cells(torch.zeros((), dtype=torch.float64, device=X.device), X, Y,
+                           lambda s, rows: _softplus64(s + bx[rows, None] + by[None, :]).sum())
+    total = _add_observed(total, ptr, idx, X, Y, observed)
     return float(total - 0.5 * float(regularization) * ((X * X).sum() + (Y * Y).sum()))
 
 
@@ -1006,16 +1032,9 @@ class LMF(_RowFit):
         hbx, hby = torch.zeros_like(bx), torch.zeros_like(by)
         D = torch.empty((max(n_users, n_items), self.factors), dtype=torch.float32, device="cuda")
         dsum = torch.empty(max(n_users, n_items), dtype=torch.float32, device="cuda")
-        for it in range(self.iterations):
-            self._half(csr_u, Y, by, X, bx, Hx, hbx, D, dsum, err)
-            if it == 0:
-                self._ids_checked(err)
-            self._half(csr_i, X, bx, Y, by, Hy, hby, D, dsum, err)
-            if callback is not None:
-                self.user_factors, self.item_factors, self.user_bias, self.item_bias = X, Y, bx, by
-                callback(it, self)
-        self.user_factors, self.item_factors, self.user_bias, self.item_bias = X, Y, bx, by
-        return self
+        return self._iterate(lambda: self._half(csr_u, Y, by, X, bx, Hx, hbx, D, dsum, err),
+                             lambda: self._half(csr_i, X, bx, Y, by, Hy, hby, D, dsum, err), err,
+                             {"user_factors": X, "item_factors": Y, "user_bias": bx, "item_bias": by}, callback)
 
     def objective(self):
         """lmf_objective of the fitted tables (a Python float; monitoring and tests)."""
@@ -1192,17 +1211,10 @@ def sgns_objective(C, U, V, negative, noise, regularization):
     dev = U.device
     ptr, idx, val = ptr.to(dev), idx.to(dev), val.to(device=dev, dtype=torch.float64)
     P = torch.as_tensor(noise).to(device=dev, dtype=torch.float64)
-    rows = _csr_rows(ptr)
-    n = int(U.shape[0])
-    cnt = torch.zeros(n, dtype=torch.float64, device=dev).index_add_(0, rows, val)
-    step = max(1, _LMF_CELLS // max(1, int(V.shape[0])))
-    total = torch.zeros((), dtype=torch.float64, device=dev)
-    for r0 in range(0, n, step):
-        s = U[r0:r0 + step] @ V.T
-        total = total - float(negative) * (cnt[r0:r0 + step, None] * (_softplus64(s) * P[None, :])).sum()
-    for i in range(0, int(idx.numel()), 1 << 20):
-        r, j = rows[i:i + (1 << 20)], idx[i:i + (1 << 20)].to(torch.int64)
-        total = total - (val[i:i + (1 << 20)] * _softplus64(-(U[r] * V[j]).sum(1))).sum()
+    cnt = torch.zeros(int(U.shape[0]), dtype=torch.float64, device=dev).index_add_(0, _csr_rows(ptr), val)
+    total = _sub_all_cells(torch.zeros((), dtype=torch.float64, device=dev), U, V, lambda s, rows:
+                           float(negative) * (cnt[rows, None] * (_softplus64(s) * P[None, :])).sum())
+    total = _add_observed(total, ptr, idx, U, V, lambda s, r, j, sl: -(val[sl] * _softplus64(-s)).sum())
     return float(total - 0.5 * float(regularization) * ((U * U).sum() + (V * V).sum()))
 
 
@@ -1347,13 +1359,8 @@ class Node2Vec(_RowFit):
             n = int(graph_csr[3])
             C = n2v_cooccurrence(self.walks, n, self.context)
         else:
-            ptr, idx, val, n = cooccurrence[:4]
-            n = int(n)
-            C = (torch.as_tensor(ptr).to(device="cuda", dtype=torch.int64).contiguous(),
-                 torch.as_tensor(idx).to(device="cuda", dtype=torch.int32).contiguous(),
-                 torch.as_tensor(val).to(device="cuda", dtype=torch.float32).contiguous(), n, n)
-            if int(C[0].numel()) != n + 1 or int(C[1].numel()) != int(C[2].numel()):
-                raise ValueError("Node2Vec: the CSR arrays do not fit together")
+            n = int(cooccurrence[3])
+            C = self._csr_arrays(*cooccurrence[:3], n) + (n, n)
         cnt = torch.zeros(n, dtype=torch.float64, device="cuda").index_add_(0, _csr_rows(C[0]), C[2].double()).cpu()
         if not float(cnt.sum()) > 0:
             raise ValueError("Node2Vec: the walks hold no pair (a graph without edges, or walk_length 1)")
@@ -1362,22 +1369,13 @@ class Node2Vec(_RowFit):
         pw = np.where(c64 > 0, c64 ** self.ns_exponent, 0.0)  # a node that never occurs has no noise mass
         P = torch.from_numpy((pw / pw.sum()).astype(np.float32)).cuda()
         KN = (self.negative * cnt).to(torch.float32).cuda()
-        gen = None if self.random_state is None else torch.Generator().manual_seed(int(self.random_state))
-        U = self._table(embedding, n, gen)
-        V = self._table(context_factors, n, gen)
+        U, V, err = self._tables(embedding, context_factors, n, n)
         Hu, Hv = torch.zeros_like(U), torch.zeros_like(V)
         D = torch.empty((n, self.factors), dtype=torch.float32, device="cuda")
-        err = torch.zeros(1, dtype=torch.int32, device="cuda")
         self.cooccurrence, self.noise = C, P
-        for it in range(self.iterations):
-            self._half(C, P, KN, V, U, Hu, D, err)
-            if it == 0 and int(err):
-                raise IndexError(f"Node2Vec: co-occurrence ids out of range for {n} nodes")
-            self._half(C, KN, P, U, V, Hv, D, err)
-            if callback is not None:
-                self.embedding, self.context_factors = U, V
-                callback(it, self)
-        self.embedding, self.context_factors = U, V
+        self._iterate(lambda: self._half(C, P, KN, V, U, Hu, D, err), lambda: self._half(C, KN, P, U, V, Hv, D, err),
+                      err, {"embedding": U, "context_factors": V}, callback,
+                      f"co-occurrence ids out of range for {n} nodes")
         self.user_factors, self.item_factors = V, U  # similar_items: over the embedding
         return self
 

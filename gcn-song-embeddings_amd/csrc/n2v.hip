@@ -7,21 +7,19 @@
 // of 10 n walks hide each other's latency.  Every draw is keyed by (seed, step,
 // try, walk position), so lanes diverge in their try counts without consequence.
 //
-// The dense term is the WEIGHT form of sig_dense_kernel (sig_dense.h).
-// sgns_update_kernel: the sparse part and the AdaGrad step on the row plan of
-// rowplan.h, as lmf_update_kernel without biases and with the row weight on D.
+// The skip-gram fit is the WEIGHT form of the two kernels of the logistic fits:
+// sig_dense_kernel (sig_dense.h) for the dense term, sig_update_kernel
+// (sig_update.h) for the sparse part and the AdaGrad step.
 #include <cmath>
 
 #include "n2v.h"
 #include "philox.h"
-#include "rowplan.h"
-#include "sig_dense.h"
+#include "sig_update.h"
 
 namespace ps {
 
 constexpr int kN2vBlock = 256;
 constexpr int kN2vTries = 256;
-constexpr float kSgnsEps = 1e-6f;
 
 struct N2vArgs {
   const int64_t* ptr;
@@ -135,68 +133,6 @@ int launch_sgns_dense(const float* X, int64_t n_rows, int64_t ldx, const float* 
   return kOk;
 }
 
-struct SgnsUpArgs {
-  const int64_t* ptr;
-  const float* rw;
-  int64_t n_rows;
-  RowItems I;
-  float* X;
-  int64_t ldx;
-  int f;
-  const float* D;
-  int64_t ldd;
-  float* H;
-  int64_t ldh;
-  float reg, lr;
-};
-
-// LONG: called by every wave of the workgroup; barriers inside.
-template <bool LONG>
-__device__ __forceinline__ void sgns_row(const SgnsUpArgs& A, int64_t row, float* __restrict__ part, int lane,
-                                         int wv) {
-  const int f = A.f, c0 = 2 * lane < f ? 2 * lane : 0;
-  const bool on = 2 * lane < f;
-  const int64_t b = A.ptr[row], e = A.ptr[row + 1];
-  float* xr = A.X + row * A.ldx + c0;
-  float* hr = A.H + row * A.ldh + c0;
-  const float2 x = row_ld2(xr, on);
-  // the sum over the row's items of w_i y_i
-  float2 acc = make_float2(0.f, 0.f);
-  row_walk<false>(A.I, b, e, LONG ? wv : 0, LONG ? kRowWaves : 1, lane, c0, on,
-                  [&](float2 y, float cu, float) __attribute__((always_inline)) {
-                    const float s = wave_sum(fmaf(x.x, y.x, x.y * y.y));
-                    const float w = cu * lmf_sigmoid(-s);
-                    acc.x = fmaf(w, y.x, acc.x);
-                    acc.y = fmaf(w, y.y, acc.y);
-                  });
-  if constexpr (LONG) {
-    float none = 0.f;
-    acc = row_wave_order_sum<false, false>(part, kRowMaxF, nullptr, lane, wv, c0, on, acc, none);
-    if (wv != 0) return;  // wave 0 has the sums and finishes the row
-  }
-  if (on) {
-    const float nrw = -A.rw[row];
-    const float2 d = *reinterpret_cast<const float2*>(A.D + row * A.ldd + c0);
-    float2 hh = *reinterpret_cast<const float2*>(hr);
-    const float gx = fmaf(-A.reg, x.x, fmaf(nrw, d.x, acc.x)), gy = fmaf(-A.reg, x.y, fmaf(nrw, d.y, acc.y));
-    hh.x = fmaf(gx, gx, hh.x);
-    hh.y = fmaf(gy, gy, hh.y);
-    *reinterpret_cast<float2*>(hr) = hh;
-    if (A.lr != 0.f)
-      *reinterpret_cast<float2*>(xr) =
-          make_float2(x.x + A.lr * gx / sqrtf(kSgnsEps + hh.x), x.y + A.lr * gy / sqrtf(kSgnsEps + hh.y));
-  }
-}
-
-__global__ __launch_bounds__(64 * kRowWaves) void sgns_update_kernel(SgnsUpArgs A) {
-  __shared__ __attribute__((aligned(16))) float part[kRowWaves * kRowMaxF];
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  row_block(
-      A.ptr, A.n_rows, (int64_t)blockIdx.x * kRowWaves, wv,
-      [&](int64_t row) __attribute__((always_inline)) { sgns_row<false>(A, row, part, lane, wv); },
-      [&](int64_t row) __attribute__((always_inline)) { sgns_row<true>(A, row, part, lane, wv); });
-}
-
 int launch_sgns_update(const int64_t* ptr, const int32_t* idx, const float* val, const float* rw, int64_t n_rows,
                        const float* Y, int64_t n_other, int64_t ldy, float* X, int64_t ldx, int64_t f, const float* D,
                        int64_t ldd, float* H, int64_t ldh, float reg, float lr, int* err, hipStream_t st) {
@@ -207,9 +143,9 @@ int launch_sgns_update(const int64_t* ptr, const int32_t* idx, const float* val,
              "sgns_update: reg and lr must be non-negative and finite");
   if (n_rows == 0) return kOk;
   // alpha = 1: the walk's weight is 1.f * val, exactly val
-  const SgnsUpArgs A{ptr, rw, n_rows, {idx, val, 1.f, Y, nullptr, n_other, ldy, err}, X, ldx, (int)f, D, ldd, H, ldh,
-                     reg, lr};
-  hipLaunchKernelGGL(sgns_update_kernel, dim3((unsigned)ceil_div(n_rows, kRowWaves)), dim3(64 * kRowWaves), 0, st, A);
+  const SigUpdateArgs A{ptr, n_rows, {idx, val, 1.f, Y, nullptr, n_other, ldy, err}, X, nullptr, ldx, (int)f, D, ldd,
+                        nullptr, rw, H, ldh, nullptr, reg, lr};
+  sig_update_launch<true>(A, st);
   PS_CHECK_LAUNCH();
   return kOk;
 }

@@ -1,4 +1,5 @@
-// The row plan of the row-wise fits (als.hip, lmf.hip, n2v.hip): a workgroup of kRowWaves
+// The row plan of the row-wise fits' two kernels (als_half_kernel in als.hip,
+// sig_update_kernel in sig_update.h for lmf.hip and n2v.hip): a workgroup of kRowWaves
 // waves owns a block of kRowWaves consecutive CSR rows.  A lane owns columns
 // 2 lane and 2 lane + 1 of every f-vector, so a gathered row of Y is one 8-byte
 // load per lane.  An ordinary row (at most kRowLong items) is one wave's, its

@@ -21,7 +21,9 @@
 //     for the same two items, (t & 3) + 8 (t >> 2) + 4h, read from the LDS tile.
 // Rows are MFMA columns, which never mix; items are summed in one fixed order;
 // nothing depends on the grid.  The two forms differ in the line that turns a
-// score into a probability and in the row sums, nowhere else.
+// score into a probability and in the row sums, nowhere else.  The sparse part
+// and the AdaGrad step that consume D are sig_update_kernel (sig_update.h), in
+// the same two forms.
 #pragma once
 #include "rowplan.h"
 

@@ -133,5 +133,5 @@ def implied_gradient(x_old, x_new, h_new):
 
 
 def row_form(length, long_row):
-    """Which form of lmf_update_kernel takes a row of `length` items."""
+    """Which form of sig_update_kernel takes a row of `length` items."""
     return "workgroup" if length > long_row else "wave"

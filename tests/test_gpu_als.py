@@ -22,37 +22,15 @@ import torch
 import als_util as au
 import parity_util as pu
 from conftest import golden
+from rowfit_util import PAD, SENT, _padded, _unpad
 
 pytestmark = pytest.mark.gpu
 
 ERR_ARG = -2       # pinsage_status (include/pinsage_hip.h)
-SENT = -123.0
-PAD = 8            # sentinel values behind every output
 REG = 0.01
 
 
 # ----------------------------------------------------------------------------- launch helpers
-def _padded(a, ld, tail=False):
-    """float32 [n, f] as a flat device buffer of rows ld apart, NaN in the
-    padding columns, PAD sentinels behind it if asked."""
-    n, f = a.shape
-    buf = np.full((n, ld), np.nan, np.float32)
-    buf[:, :f] = a
-    flat = buf.reshape(-1)
-    if tail:
-        flat = np.concatenate([flat, np.full(PAD, SENT, np.float32)])
-    return torch.from_numpy(flat).cuda()
-
-
-def _unpad(t, n, f, ld):
-    """The live part of a padded buffer; asserts padding and tail."""
-    h = t.cpu().numpy()
-    assert (h[n * ld:] == SENT).all(), "values behind the table were written"
-    m = h[:n * ld].reshape(n, ld)
-    assert np.isnan(m[:, f:]).all(), "padding columns were written"
-    return m[:, :f].copy()
-
-
 def _gram(Y, reg, ld=None, n=None, f=None):
     """pinsage_als_gram into a sentinel-filled G: (status, G [f, f])."""
     import _native as nat

@@ -31,38 +31,16 @@ import als_util as au
 import lmf_util as lu
 import parity_util as pu
 from conftest import golden
+from rowfit_util import PAD, SENT, _padded, _unpad
 
 pytestmark = pytest.mark.gpu
 
 ERR_ARG = -2       # pinsage_status (include/pinsage_hip.h)
-SENT = -123.0
-PAD = 8            # sentinel values behind every output
 U = 2.0 ** -24
 REG, LR = 0.6, 0.1
 
 
 # ----------------------------------------------------------------------------- launch helpers
-def _padded(a, ld, tail=False):
-    """float32 [n, f] as a flat device buffer of rows ld apart, NaN in the
-    padding columns, PAD sentinels behind it if asked."""
-    n, f = a.shape
-    buf = np.full((n, ld), np.nan, np.float32)
-    buf[:, :f] = a
-    flat = buf.reshape(-1)
-    if tail:
-        flat = np.concatenate([flat, np.full(PAD, SENT, np.float32)])
-    return torch.from_numpy(flat).cuda()
-
-
-def _unpad(t, n, f, ld):
-    """The live part of a padded buffer; asserts padding and tail."""
-    h = t.cpu().numpy()
-    assert (h[n * ld:] == SENT).all(), "values behind the table were written"
-    m = h[:n * ld].reshape(n, ld)
-    assert np.isnan(m[:, f:]).all(), "padding columns were written"
-    return m[:, :f].copy()
-
-
 def _vec(a, tail=False):
     a = np.asarray(a, np.float32)
     if tail:

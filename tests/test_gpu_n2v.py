@@ -15,6 +15,8 @@ Dense kernel.  The bound is test_gpu_lmf.py's with the column weight, u = 2^-24:
 Update kernel.  New x is held against the float64 restatement by
 als_util.row_errors under the project's rule: the device's error is at most
 als_util.TOL_FACTOR (8) times the float32 restatement's on the same inputs.
+It is one kernel with pinsage_lmf_update's: with unit weights and zero biases
+the two write the same bits.
 
 Fit.  The device objective after 30 iterations ends above its start and within
 1e-4 relative of the float64 restatement run on the same counts and initial
@@ -29,12 +31,11 @@ import lmf_util as lu
 import n2v_util as nu
 import parity_util as pu
 from conftest import golden
+from rowfit_util import PAD, SENT, _padded, _unpad
 
 pytestmark = pytest.mark.gpu
 
 ERR_ARG = -2
-SENT = -123.0
-PAD = 8
 U = 2.0 ** -24
 N_WALKS, LENGTH = 257, 20
 P_Q = [(2.0, 0.5), (0.5, 2.0), (1.0, 1.0), (16.0, 1.0), (4.0, 0.25), (0.25, 4.0)]
@@ -185,24 +186,6 @@ def test_walk_refusals_and_bad_ids():
 
 
 # ----------------------------------------------------------------------------- launch helpers
-def _padded(a, ld, tail=False):
-    n, f = a.shape
-    buf = np.full((n, ld), np.nan, np.float32)
-    buf[:, :f] = a
-    flat = buf.reshape(-1)
-    if tail:
-        flat = np.concatenate([flat, np.full(PAD, SENT, np.float32)])
-    return torch.from_numpy(flat).cuda()
-
-
-def _unpad(t, n, f, ld):
-    h = t.cpu().numpy()
-    assert (h[n * ld:] == SENT).all(), "values behind the table were written"
-    m = h[:n * ld].reshape(n, ld)
-    assert np.isnan(m[:, f:]).all(), "padding columns were written"
-    return m[:, :f].copy()
-
-
 def _dense(X, Y, cw, pad_x=0, pad_y=0, pad_d=0):
     """pinsage_sgns_dense into a sentinel-filled output: (status, D [n, f])."""
     import _native as nat
@@ -427,6 +410,35 @@ def test_update_refusals_leave_the_outputs_untouched():
                {"rw": None}, {"ptr": None}):
         assert update(**kw) == (ERR_ARG, True), kw
         assert L.pinsage_last_error()
+
+
+@pytest.mark.parametrize("f", [4, 60, 128])
+def test_update_is_the_bias_form_without_biases(f):
+    """What the one sig_update_kernel rests on: with alpha = 1 and zero bx, by and
+    hb, pinsage_lmf_update leaves the X and H that pinsage_sgns_update leaves
+    with rw = 1, bit for bit.  (s + 0) + 0 is s, 1 val is val and acc - d rounds
+    as fmaf(-1, d, acc) does; dsum moves the biases only."""
+    import _native as nat
+    csr, _, X, H, Y, D = _update_case(f, seed=90 + f)
+    ptr, idx, val, n, m = csr
+    ld = f + 4
+    rc, xw, hw, err = _update(csr, np.ones(n), X, H, Y, D, pad=4, forms=["wave", "workgroup"])
+    assert rc == 0 and err == 0
+    xd, hd = _padded(X, ld, tail=True), _padded(H, ld, tail=True)
+    yd, dd = _padded(Y, ld), _padded(D, ld)
+    t = [torch.from_numpy(np.ascontiguousarray(a)).cuda() for a in (ptr, idx, val)]
+    bx, by, hb = (torch.zeros(k, device="cuda") for k in (n, m, n))
+    dsum = torch.from_numpy(np.random.default_rng(f).random(n).astype(np.float32)).cuda()
+    errd = torch.zeros(1, dtype=torch.int32, device="cuda")
+    rc = nat.lib().pinsage_lmf_update(nat.ptr(t[0]), nat.ptr(t[1]), nat.ptr(t[2]), n, nat.ptr(yd), nat.ptr(by), m, ld,
+                                      nat.ptr(xd), nat.ptr(bx), ld, f, nat.ptr(dd), ld, nat.ptr(dsum), nat.ptr(hd), ld,
+                                      nat.ptr(hb), 1.0, REG, LR, nat.ptr(errd), nat.stream_ptr())
+    torch.cuda.synchronize()
+    assert rc == 0 and int(errd) == 0
+    xb, hn = _unpad(xd, n, f, ld), _unpad(hd, n, f, ld)
+    assert not np.array_equal(xb, X) and np.isfinite(xb).all()
+    assert torch.equal(torch.from_numpy(xb), torch.from_numpy(xw)), np.argwhere(xb != xw)[:1]
+    assert torch.equal(torch.from_numpy(hn), torch.from_numpy(hw)), np.argwhere(hn != hw)[:1]
 
 
 # ----------------------------------------------------------------------------- Node2Vec.fit
