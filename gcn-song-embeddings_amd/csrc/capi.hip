@@ -15,6 +15,7 @@
 #include "capi.h"
 #include "conv.h"
 #include "cooc.h"
+#include "dq.h"
 #include "fly.h"
 #include "frontier.h"
 #include "gemm.h"
@@ -855,46 +856,13 @@ int pinsage_weighted_agg(const float* q, int64_t hid, const int32_t* loc, const 
   return launch_agg(q, (int)hid, loc, w, (int)T, nullptr, n_rows, agg, (hipStream_t)stream);
 }
 
-// scratch of pinsage_agg_transpose: the buffers the engine carves per layer
-// for its CSR transpose and dq chunk list (engine.hip, LayerBuf), same sizes
-struct AggTScratch {
-  int64_t cnt, bsum, off, cursor, cbase, occ2, occ2b, chunks, nchunks, split, nsplit, part, tk, bytes;
-  int64_t max_chunks, max_split;
-};
 static bool agg_transpose_shape_ok(int64_t S, int64_t T, int64_t N, int64_t hid) {
   return S >= 1 && T >= 1 && T <= 64 && N >= 1 && hid >= 4 && hid % 4 == 0 && hid <= 65536 &&
          S * T <= INT32_MAX - 64 && N <= INT32_MAX - 64;
 }
-static AggTScratch agg_transpose_layout(int64_t S, int64_t T, int64_t N, int64_t hid) {
-  AggTScratch a{};
-  int64_t cur = 0;
-  auto carve = [&cur](int64_t bytes) {
-    const int64_t at = cur;
-    cur += align_up(bytes, 256);
-    return at;
-  };
-  a.max_chunks = dq_chunk_capacity(S, (int)T, N);
-  a.max_split = dq_split_capacity(S, (int)T);
-  a.cnt = carve((N + 1) * 4);
-  a.tk = carve((int64_t)dq_tree_levels(a.max_chunks) * a.max_chunks * 4);
-  a.bsum = carve((int64_t)ceil_div(N + 1, 1024) * 8 + 16);
-  a.off = carve((N + 1) * 4);
-  a.cursor = carve((N + 1) * 4);
-  a.cbase = carve((N + 1) * 4);
-  a.occ2 = carve(a.max_chunks * 16 * 8);
-  a.occ2b = carve(a.max_chunks * 16 * 8);
-  a.chunks = carve(a.max_chunks * 8);
-  a.nchunks = carve(16);
-  a.split = carve(a.max_split * 8);
-  a.nsplit = carve(16);
-  a.part = carve(a.max_chunks * hid * 4);
-  a.bytes = cur;
-  return a;
-}
-
 int64_t pinsage_agg_transpose_scratch_bytes(int64_t n_rows_max, int64_t T, int64_t n_q_max, int64_t hid) {
   if (!agg_transpose_shape_ok(n_rows_max, T, n_q_max, hid)) return -1;
-  return agg_transpose_layout(n_rows_max, T, n_q_max, hid).bytes;
+  return dq_layout(n_rows_max, (int)T, n_q_max, (int)hid).bytes;
 }
 
 int pinsage_agg_transpose(const int32_t* loc, const float* w, const int* n_rows_dev, int64_t n_rows_max, int64_t T,
@@ -911,55 +879,11 @@ int pinsage_agg_transpose(const int32_t* loc, const float* w, const int* n_rows_
   PS_REQUIRE(!dpq_planes || (mode == 1 && plane_stride >= n_q_max * hid && plane_stride % 4 == 0), kErrArg,
              "agg_transpose: planes output needs mode 1 (hid <= 512) and a plane stride >= n_q_max * hid, "
              "a multiple of 4");
-  const AggTScratch a = agg_transpose_layout(n_rows_max, T, n_q_max, hid);
-  char* sc = static_cast<char*>(scratch);
-  auto at_i = [sc](int64_t o) { return reinterpret_cast<int*>(sc + o); };
-  auto at_2 = [sc](int64_t o) { return reinterpret_cast<int2*>(sc + o); };
+  const DqPlan plan{dq_layout(n_rows_max, (int)T, n_q_max, (int)hid), scratch};
   hipStream_t st = (hipStream_t)stream;
   PS_TRY(csr_prepare());
-  CsrBuildParams cb;
-  cb.loc = loc;
-  cb.wloc = w;
-  cb.nS = n_rows_dev;
-  cb.S_max = n_rows_max;
-  cb.T = (int)T;
-  cb.nN = n_q_dev;
-  cb.N_max = n_q_max;
-  cb.hid = (int)hid;
-  cb.cnt = at_i(a.cnt);
-  cb.bsum = at_i(a.bsum);
-  cb.off = at_i(a.off);
-  cb.cursor = at_i(a.cursor);
-  cb.cbase = at_i(a.cbase);
-  cb.occ2 = at_2(a.occ2);
-  cb.chunks = at_2(a.chunks);
-  cb.nchunks = at_i(a.nchunks);
-  cb.split = at_2(a.split);
-  cb.nsplit = at_i(a.nsplit);
-  cb.occ2_tmp = at_2(a.occ2b);
-  PS_TRY(launch_csr_build(cb, st));
-  DqChunkParams dq;
-  dq.chunks = cb.chunks;
-  dq.nchunks = cb.nchunks;
-  dq.max_chunks = a.max_chunks;
-  dq.split = cb.split;
-  dq.nsplit = cb.nsplit;
-  dq.max_split = a.max_split;
-  dq.off = cb.off;
-  dq.occ2 = cb.occ2;
-  dq.dagg = dagg;
-  dq.ld_dagg = ld_dagg;
-  dq.q = q;
-  dq.hid = (int)hid;
-  dq.dpq = dpq;
-  dq.part = reinterpret_cast<float*>(sc + a.part);
-  if (mode == 1) {
-    dq.cbase = cb.cbase;
-    dq.tk = at_i(a.tk);
-  }
-  dq.dpq3 = dpq_planes;
-  dq.ps3 = plane_stride;
-  return launch_dq_chunks(dq, st);
+  PS_TRY(launch_csr_build(plan, loc, w, n_rows_dev, n_q_dev, st));
+  return launch_dq_chunks(plan, dagg, ld_dagg, q, dpq, dpq_planes, plane_stride, mode == 1, st);
 }
 
 int64_t pinsage_fly_workspace_bytes(int64_t n, int64_t B, int64_t n_layers, int64_t T, int64_t n_hops) {

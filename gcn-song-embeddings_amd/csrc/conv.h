@@ -78,71 +78,6 @@ int launch_reduce_slabs_2d(const float* part, int S, int64_t stride, int M, int 
 int launch_agg(const float* q, int hid, const int32_t* loc, const float* wloc, int T,
                const int* nS, int64_t S_max, float* agg, hipStream_t st);
 
-// dynamic LDS above 64 KiB must be allowed per kernel (once, outside capture)
-int csr_prepare();
-
-// CSR of the neighbour slots by q row, plus the dq chunk list.  cnt must be
-// zero on entry (zeroed once by pinsage_engine_init_workspace, then left zero
-// by the scan).
-struct CsrBuildParams {
-  const int32_t* loc = nullptr;  // [S][T] q row of every slot (LayerPrep::loc)
-  const float* wloc = nullptr;   // [S][T] the slots' weights
-  const int* nS = nullptr;       // device row count of S (<= S_max)
-  int64_t S_max = 0;
-  int T = 0;
-  const int* nN = nullptr;       // device row count of the q rows (<= N_max)
-  int64_t N_max = 0;
-  int hid = 0;
-  int* cnt = nullptr;            // [N + 1] slots per q row
-  int* bsum = nullptr;           // block sums of the two-launch scan
-  int* off = nullptr;            // [N + 1] out: row starts
-  int* cursor = nullptr;         // [N + 1] fill cursors
-  int* cbase = nullptr;          // [N + 1] out: first chunk of every row
-  int2* occ2 = nullptr;          // out: (source row, weight bits) pairs by q row
-  int2* chunks = nullptr;        // out: the dq chunk list (dq_chunk_capacity entries)
-  int* nchunks = nullptr;
-  int2* split = nullptr;         // out: rows of more than one chunk (dq_split_capacity entries)
-  int* nsplit = nullptr;
-  // set: pairs sorted by source row within a q row (bitwise-reproducible sums);
-  // scratch of occ2's size
-  int2* occ2_tmp = nullptr;
-};
-int launch_csr_build(const CsrBuildParams& p, hipStream_t st);
-
-// upper bound of the dq chunk list: one partial chunk per row plus full ones
-int64_t dq_chunk_capacity(int64_t S_max, int T, int64_t N_max);
-// upper bound of the split-row list: a split row holds more than kDqChunk slots
-int64_t dq_split_capacity(int64_t S_max, int T);
-// levels of the split-row tree for rows of up to max_chunks chunks (fan-in 8)
-int dq_tree_levels(int64_t max_chunks);
-
-// The aggregation's transpose over launch_csr_build's plan: dpq[u] = lrelu'(q[u])
-// * the weighted sum of the dagg rows (row stride ld_dagg) whose slots name q row u.
-struct DqChunkParams {
-  const int2* chunks = nullptr;
-  const int* nchunks = nullptr;
-  int64_t max_chunks = 0;
-  const int2* split = nullptr;
-  const int* nsplit = nullptr;
-  int64_t max_split = 0;
-  const int* off = nullptr;
-  const int2* occ2 = nullptr;
-  const float* dagg = nullptr;
-  int64_t ld_dagg = 0;
-  const float* q = nullptr;
-  int hid = 0;
-  float* dpq = nullptr;
-  float* part = nullptr;  // [max_chunks][hid] chunk partials
-  // split-row tree (cbase and tk set, hid <= 512): split rows combined by their
-  // own chunks, no combine launch; tk: dq_tree_levels x max_chunks zeroed ints
-  const int* cbase = nullptr;
-  int* tk = nullptr;
-  // with the tree: dpq also written as hi / mid / lo bf16 planes, plane stride ps3
-  uint16_t* dpq3 = nullptr;
-  int64_t ps3 = 0;
-};
-int launch_dq_chunks(const DqChunkParams& p, hipStream_t st);
-
 // dp = the backward of y = normalize(lrelu(.)) for nrows (device, <= max_rows)
 // rows of n floats; also zeroes z (*z_rows x z_n floats, nullable) and zi
 // (zi_n ints, nullable)

@@ -26,6 +26,7 @@
 #include "aggw.h"
 #include "common.h"
 #include "conv.h"
+#include "dq.h"
 #include "frontier.h"
 #include "gemm.h"
 #include "head.h"
@@ -56,11 +57,9 @@ struct LayerBuf {
   size_t q = 0, agg = 0, y = 0, nrm = 0;
   size_t wplanes = 0;  // the W weight's fragment-order bf16 planes (aggw.hip pipelined form)
   // backward
-  size_t dY = 0, dp = 0, dagg = 0, dpq = 0, cnt = 0, bsum = 0, off = 0, cursor = 0, cbase = 0,
-         occ2 = 0, occ2b = 0, chunks = 0, nchunks = 0, dqpart = 0, split = 0, nsplit = 0;
-  int64_t max_chunks = 0, max_split = 0;
-  size_t dqtk = 0;  // split-row tree tickets (dq_tree_levels x max_chunks ints, self-resetting)
-  int64_t dqtk_len = 0;
+  size_t dY = 0, dp = 0, dagg = 0, dpq = 0;
+  size_t dq = 0;  // the transposed aggregation's plan (dq.h)
+  DqLayout dq_lay;
   // parameter offsets (floats) into the flat param / grad buffers
   int64_t pQw = 0, pQb = 0, pWw = 0, pWb = 0;
   // this layer's own neighbourhood table (pinsage_engine_set_layer_table: the
@@ -142,7 +141,7 @@ struct Engine {
   int kw_side_wg = getenv("PINSAGE_KW_SIDE_WG") ? atoi(getenv("PINSAGE_KW_SIDE_WG")) : 128;
   // PINSAGE_DQ_TREE (default 1): rows of the transposed aggregation split over
   // several chunks are summed by their chunk waves as a fixed fan-in-8 tree
-  // (conv.hip dq_tree_leaf) instead of by a dq_combine launch after them
+  // (dq.hip dq_tree_leaf) instead of by a dq_combine launch after them
   // (three interleaved pairs at C2, ms/step: 0.3949 / 0.3975 / 0.3985 with the
   // combine launch, 0.3872 / 0.3855 / 0.3939 without; C4 even)
   int dq_tree = getenv("PINSAGE_DQ_TREE") ? atoi(getenv("PINSAGE_DQ_TREE")) : 1;
@@ -453,22 +452,8 @@ static void layout(Engine& E) {
     lb.dp = carve(cur, FS * c.out * 4);
     lb.dagg = carve(cur, FS * c.hid * 4);
     lb.dpq = carve(cur, FN * c.hid * 4);
-    lb.cnt = carve(cur, (FN + 1) * 4);
-    lb.bsum = carve(cur, (int64_t)ceil_div(FN + 1, 1024) * 8 + 16);
-    lb.off = carve(cur, (FN + 1) * 4);
-    lb.cursor = carve(cur, (FN + 1) * 4);
-    lb.max_chunks = dq_chunk_capacity(FS, (int)T, FN);
-    lb.cbase = carve(cur, (FN + 1) * 4);
-    lb.occ2 = carve(cur, lb.max_chunks * 16 * 8);  // {row, weight} pairs, 16 per chunk
-    lb.occ2b = carve(cur, lb.max_chunks * 16 * 8);  // (split rows' canonical reorder)
-    lb.chunks = carve(cur, lb.max_chunks * 8);
-    lb.nchunks = carve(cur, 16);
-    lb.dqpart = carve(cur, lb.max_chunks * c.hid * 4);  // partials of split dq rows
-    lb.max_split = dq_split_capacity(FS, (int)T);
-    lb.split = carve(cur, lb.max_split * 8);
-    lb.nsplit = carve(cur, 16);
-    lb.dqtk_len = (int64_t)dq_tree_levels(lb.max_chunks) * lb.max_chunks;
-    lb.dqtk = carve(cur, lb.dqtk_len * 4);
+    lb.dq_lay = dq_layout(FS, (int)T, FN, (int)c.hid);
+    lb.dq = carve(cur, lb.dq_lay.bytes);
   }
   const int64_t top = E.L.back().S.cap;
   E.ids = carve(cur, c.max_pos * 8 + 16);  // + Adam coefficients staged behind the ids
@@ -660,27 +645,8 @@ static int engine_frontier(Engine& E, void* ws, const int64_t* ids_dev, int64_t 
     LayerBuf& lb = E.L[(size_t)l];
     hipStream_t sl = (csr_fork == 1 && l == 0) ? s_fk : st;
     Timed tc(E, lname("fwd.csr", l), sl);
-    CsrBuildParams cb;
-    cb.loc = at<int32_t>(ws, lb.loc);
-    cb.wloc = at<float>(ws, lb.wloc);
-    cb.nS = cnt(lb.S);
-    cb.S_max = lb.S.cap;
-    cb.T = T;
-    cb.nN = cnt(lb.N);
-    cb.N_max = lb.N.cap;
-    cb.hid = (int)c.hid;
-    cb.cnt = at<int>(ws, lb.cnt);
-    cb.bsum = at<int>(ws, lb.bsum);
-    cb.off = at<int>(ws, lb.off);
-    cb.cursor = at<int>(ws, lb.cursor);
-    cb.cbase = at<int>(ws, lb.cbase);
-    cb.occ2 = at<int2>(ws, lb.occ2);
-    cb.chunks = at<int2>(ws, lb.chunks);
-    cb.nchunks = at<int>(ws, lb.nchunks);
-    cb.split = at<int2>(ws, lb.split);
-    cb.nsplit = at<int>(ws, lb.nsplit);
-    cb.occ2_tmp = at<int2>(ws, lb.occ2b);
-    PS_TRY(launch_csr_build(cb, sl));
+    PS_TRY(launch_csr_build(DqPlan{lb.dq_lay, at<char>(ws, lb.dq)}, at<int32_t>(ws, lb.loc), at<float>(ws, lb.wloc),
+                            cnt(lb.S), cnt(lb.N), sl));
   }
   if (csr_fork) PS_TRY(dep(E, s_fk, st));  // join: nothing of this call stays on side[2]
   return kOk;
@@ -1197,26 +1163,8 @@ static int engine_backward(Engine& E, void* ws, hipStream_t st, const AdamStep* 
                            a.beta1, a.beta2, a.eps, s_w);
       }));
     }
-    DqChunkParams dq;
-    dq.chunks = at<int2>(ws, lb.chunks);
-    dq.nchunks = at<int>(ws, lb.nchunks);
-    dq.max_chunks = lb.max_chunks;
-    dq.split = at<int2>(ws, lb.split);
-    dq.nsplit = at<int>(ws, lb.nsplit);
-    dq.max_split = lb.max_split;
-    dq.off = at<int>(ws, lb.off);
-    dq.occ2 = at<int2>(ws, lb.occ2);
-    dq.dagg = at<float>(ws, lb.dagg);
-    dq.ld_dagg = hd;
-    dq.q = at<float>(ws, lb.q);
-    dq.hid = hd;
-    dq.dpq = at<float>(ws, lb.dpq);
-    dq.part = at<float>(ws, lb.dqpart);
-    if (E.dq_tree) {
-      dq.cbase = at<int>(ws, lb.cbase);
-      dq.tk = at<int>(ws, lb.dqtk);
-    }
-    PS_TRY(launch_dq_chunks(dq, st));
+    PS_TRY(launch_dq_chunks(DqPlan{lb.dq_lay, at<char>(ws, lb.dq)}, at<float>(ws, lb.dagg), hd, at<float>(ws, lb.q),
+                            at<float>(ws, lb.dpq), nullptr, 0, E.dq_tree, st));
     PS_TRY(run_pend(E));
     WGrad q_wgrad;
     {
@@ -1298,10 +1246,7 @@ static int engine_init_workspace(Engine& E, void* ws, hipStream_t st) {
   PS_CHECK_HIP(hipMemsetAsync(at<char>(ws, E.G), 0, (size_t)(3 * top * c.out) * 4, st));
   PS_CHECK_HIP(hipMemsetAsync(at<char>(ws, E.Kc), 0, (size_t)(3 * top) * 4, st));
   PS_CHECK_HIP(hipMemsetAsync(at<char>(ws, E.rank_off), 0xff, 4, st));  // (no positions yet)
-  for (auto& lb : E.L) {
-    PS_CHECK_HIP(hipMemsetAsync(at<char>(ws, lb.cnt), 0, (size_t)(lb.N.cap + 1) * 4, st));
-    PS_CHECK_HIP(hipMemsetAsync(at<char>(ws, lb.dqtk), 0, (size_t)lb.dqtk_len * 4, st));
-  }
+  for (auto& lb : E.L) PS_TRY(dq_plan_zero(DqPlan{lb.dq_lay, at<char>(ws, lb.dq)}, st));
   PS_CHECK_HIP(hipMemsetAsync(at<char>(ws, E.sk_cnt), 0, (size_t)E.sk_cnt_len * 4, st));
   PS_CHECK_HIP(hipMemsetAsync(at<char>(ws, E.kw_cnt_main), 0, (size_t)E.kw_cnt_len * 4, st));
   PS_CHECK_HIP(hipMemsetAsync(at<char>(ws, E.kw_cnt_side), 0, (size_t)E.kw_cnt_len * 4, st));

@@ -1,8 +1,9 @@
 """The transposed aggregation (the backward of pinsage_model.py:202 towards the
-q rows) and the CSR build under it, through the C-ABI entry
+q rows) and the CSR build under it (csrc/dq.hip), through the C-ABI entry
 pinsage_agg_transpose (csr_count / scan / csr_fill / the canonical sorts /
 dq_chunk_kernel + dq_combine_kernel or the split-row tree, launched as the
-engine launches them), against float64 torch on the same fp32 inputs:
+engine launches them over dq.h's plan), against float64 torch on the same
+fp32 inputs:
 
   dpq[u] = lrelu'(q[u]) * sum over the slots (f, t) with loc[f][t] == u of
            w[f][t] * dagg[f]
@@ -381,8 +382,8 @@ def test_documented_summation_order_bitwise_and_reruns_on_one_scratch():
 def test_q_row_counts_through_every_csr_and_scan_regime(U, ranges, monkeypatch):
     """scan_small_kernel below, at and above 1024 per thread-run boundaries
     (U == 1024 per: the totals written by thread 1023) up to 4096 rows, the
-    two-launch scan from 4097; one LDS histogram up to 40960 q rows, two
-    (range, slice) ranges at 40961, and the per-wave global atomics there with
+    two-launch scan from 4097; one range of LDS histogram slices up to 40960 q
+    rows, two (range, slice) ranges at 40961, and the per-wave global atomics there with
     PINSAGE_CSR_RANGES=0 (read per call).  hid 16, exact sums, both modes."""
     if ranges is not None:
         monkeypatch.setenv("PINSAGE_CSR_RANGES", ranges)

@@ -593,7 +593,7 @@ def test_conv_layer_autograd_vs_oracle(dims, T, n):
 
 
 def test_csr_transpose_ranges_match_atomic_path():
-    """The backward's CSR transpose of the neighbour slots (conv.hip
+    """The backward's CSR transpose of the neighbour slots (dq.hip
     csr_count_kernel / csr_fill_kernel) beyond one LDS histogram (> 40960
     distinct layer-0 neighbours): the (range, slice) histogram path trains like
     the per-wave global-atomic path (PINSAGE_CSR_RANGES=0) -- same published
