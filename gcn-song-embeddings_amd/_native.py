@@ -192,6 +192,11 @@ _SIGS = {
     "pinsage_lmf_dense": (ctypes.c_int, [vp, vp, i64, i64, vp, vp, i64, i64, i64, vp, i64, vp, vp]),
     "pinsage_lmf_update": (ctypes.c_int, [vp, vp, vp, i64, vp, vp, i64, i64, vp, vp, i64, i64, vp, i64, vp, vp, i64,
                                           vp, f32, f32, f32, vp, vp]),
+    "pinsage_bpr_max_tries": (i64, []),
+    "pinsage_bpr_sample": (ctypes.c_int, [vp, vp, i64, i64, vp, i64, vp, vp, i64, i64, i64, i64, ctypes.c_uint64, i64,
+                                          ctypes.c_uint32, vp, vp, vp, vp]),
+    "pinsage_bpr_apply": (ctypes.c_int, [vp, vp, vp, i64, vp, i64, i64, vp, vp, i64, i64, vp, i64, vp, f32, f32, vp,
+                                         vp]),
     "pinsage_n2v_walk": (ctypes.c_int, [vp, vp, vp, i64, vp, i64, i64, f32, f32, ctypes.c_uint64, ctypes.c_uint32, i64,
                                         vp, vp, vp]),
     "pinsage_sgns_dense": (ctypes.c_int, [vp, i64, i64, vp, vp, i64, i64, i64, vp, i64, vp]),

@@ -28,7 +28,13 @@ kNN above.  ``ColTrackLMF`` / ``TrackTrackLMF`` are the same two classes with
 the fit the reference selects by algo="lmf": ``LMF``, logistic matrix
 factorisation by full-gradient AdaGrad ascent (csrc/lmf.hip: a fused
 sigmoid(X Y^T) Y MFMA kernel and a sparse update), again this package's own
-definition.
+definition.  ``ColTrackBPR`` / ``TrackTrackBPR`` are the same two classes with
+the fit the reference selects by any other algo: ``BPR``, Bayesian personalised
+ranking with negatives from the counter-based Philox generator and Jacobi
+AdaGrad half-iterations (csrc/bpr.hip: a sample kernel and a signed gathered
+row update), this package's own definition and deterministic; implicit's
+sampled SGD with racing updates is not reproduced, and the quality of the
+defaults on real data is unmeasured.
 
 ``FastNode2Vec`` (baselines.py:223-255) stands on ``Node2Vec``: second-order
 (p, q) walks by rejection sampling on the counter-based Philox generator and a
@@ -38,8 +44,8 @@ the walks' window co-occurrence counts that runs on the LMF scaffold
 kernel and a sparse update).  Again this package's own definition,
 deterministic, with no parity with fastnode2vec or gensim claimed.
 
-The reference's other baseline recommenders (implicit's bpr, networkx
-similarities, lib/gnns) are out of scope; their libraries are not part of this
+The reference's other baseline recommenders (networkx similarities, lib/gnns)
+and implicit's own sampled-SGD order for bpr are out of scope; their libraries are not part of this
 build.  Names, signatures, return types and RNG consumption
 follow the reference; compute runs in HIP (no CPU fallback).
 """
@@ -777,7 +783,7 @@ def _sub_all_cells(total, X, Y, term):
 
 
 class _RowFit:
-    """What ALS, LMF and Node2Vec share: the factor tables, the intake of the
+    """What ALS, LMF, BPR and Node2Vec share: the factor tables, the intake of the
     matrix, the iteration loop and similar_items.  ``_who`` prefixes the error
     texts."""
 
@@ -794,6 +800,14 @@ class _RowFit:
         t = torch.as_tensor(given)
         if tuple(t.shape) != (n, f):
             raise ValueError(f"{self._who}: factors of shape {tuple(t.shape)}, expected {(n, f)}")
+        return t.to(device="cuda", dtype=torch.float32, copy=True).contiguous()
+
+    def _bias(self, given, n):
+        if given is None:
+            return torch.zeros(n, dtype=torch.float32, device="cuda")
+        t = torch.as_tensor(given)
+        if tuple(t.shape) != (n,):
+            raise ValueError(f"{self._who}: a bias of shape {tuple(t.shape)}, expected {(n,)}")
         return t.to(device="cuda", dtype=torch.float32, copy=True).contiguous()
 
     def _csr_arrays(self, ptr, idx, val, n_rows):
@@ -1000,15 +1014,6 @@ class LMF(_RowFit):
         self.iterations = int(iterations)
         self.user_bias = self.item_bias = None
 
-    @staticmethod
-    def _bias(given, n):
-        if given is None:
-            return torch.zeros(n, dtype=torch.float32, device="cuda")
-        t = torch.as_tensor(given)
-        if tuple(t.shape) != (n,):
-            raise ValueError(f"LMF: a bias of shape {tuple(t.shape)}, expected {(n,)}")
-        return t.to(device="cuda", dtype=torch.float32, copy=True).contiguous()
-
     def _half(self, csr, Y, by, X, bx, H, hb, D, dsum, err):
         ptr, idx, val, n_rows, n_other = csr
         L, f = nat.lib(), self.factors
@@ -1042,8 +1047,199 @@ class LMF(_RowFit):
                              self.item_bias, self.regularization, self.alpha)
 
 
+BPR_MAX_FACTORS = ALS_MAX_FACTORS
+BPR_MAX_TRIES = 16     # pinsage_bpr_max_tries(): tries per sample before it is void
+BPR_MAX_NEGATIVES = 8  # kBprMaxNeg (csrc/bpr.hip)
+
+
+def bpr_objective(user_items, X, Y, b, neg, negatives, regularization):
+    """The BPR objective of one draw (to be maximised)
+
+        sum_t ln sig(z_t) - (reg / 2)(|X|^2 + |Y|^2)   over the non-void samples t,
+        z_t = (x_u . y_i + b_i) - (x_u . y_j + b_j),   j = neg[t] >= 0,
+
+    where sample t = e * negatives + s belongs to the e-th stored cell (u, i) of
+    user_items.  In float64, plain torch, on the factors' device."""
+    ptr, idx = user_items[:2]
+    X, Y = X.to(torch.float64), Y.to(torch.float64)
+    dev = X.device
+    b = torch.as_tensor(b).to(device=dev, dtype=torch.float64)
+    S = int(negatives)
+    u = _csr_rows(ptr.to(dev)).repeat_interleave(S)
+    i = idx.to(device=dev, dtype=torch.int64).repeat_interleave(S)
+    j = torch.as_tensor(neg).to(device=dev, dtype=torch.int64).reshape(-1)
+    if int(j.numel()) != int(i.numel()):
+        raise ValueError(f"bpr_objective: {int(j.numel())} negatives for {int(i.numel())} samples")
+    ok = j >= 0
+    u, i, j = u[ok], i[ok], j[ok]
+    z = (X[u] * (Y[i] - Y[j])).sum(1) + b[i] - b[j]
+    return float(-_softplus64(-z).sum() - 0.5 * float(regularization) * ((X * X).sum() + (Y * Y).sum()))
+
+
+class BPR(_RowFit):
+    """Bayesian personalised ranking (Rendle, Freudenthaler, Gantner,
+    Schmidt-Thieme, "BPR: Bayesian Personalized Ranking from Implicit Feedback",
+    2009) on the kernels of csrc/bpr.hip: what the reference takes from
+    implicit's BayesianPersonalizedRanking with algo="bpr".  The model is THIS
+    PROJECT'S DEFINITION, deterministic and stated here in full: negatives from
+    the counter-based Philox generator and Jacobi AdaGrad half-iterations, not
+    that package's sampled SGD with racing updates, its popularity-proportional
+    negatives or its per-step regularisation.  The package cannot be run here
+    and no parity with its numbers is claimed; the quality of the defaults on
+    real data is unmeasured.
+
+    Inputs and tables.
+    - R [n_users, n_items] is the usual CSR tuple.
+    - Rows are strictly ascending.  ``fit`` checks this and raises ValueError
+      otherwise, because the negative draw binary-searches the row.
+    - Only R's structure is used.  Every stored cell is one positive; values
+      pass the usual check (finite, > 0) and are otherwise ignored.
+    - Tables: X [n_users, f], Y [n_items, f] and an item bias b [n_items].
+      There is no user bias.
+    - Cell e is the e-th stored cell of R.
+    - Sample t = e * S + s, for s < S = ``negatives``.
+
+    The draw.  For draw round rho, sample t of a cell (u, i), and tries
+    k = 0 .. 15:
+
+        (r0, r1, r2, r3) = Philox4x32-10(key = seed, ctr = (rho * 16 + k, t lo, t hi, offset))
+        j = (uint64(r0) * n_items) >> 32
+        accept the first j that is not a column of row u   (binary search; j == i is therefore rejected)
+
+    - After 16 rejected tries the sample is void: neg[t] = -1, w[t] = 0.
+    - Otherwise neg[t] = j.
+    - With z = (x_u . y_i + b_i) - (x_u . y_j + b_j), set w[t] = sig(-z).
+    - The dot is the row plan's: two columns per lane,
+      fmaf(x.x, y.x, x.y * y.y), then the wave sum.  The sigmoid is LMF's.
+    - neg and w of sample t depend on (seed, rho, offset, t, row u, the tables)
+      only.  They do not depend on the grid or on batching.  ``fit`` uses
+      offset 0.
+
+    One iteration ``it``.
+    - The user half uses draw round 2 it.
+    - The item half uses round 2 it + 1 and the new X.
+    - Both halves are Jacobi.
+    - User half, row u, entries in ascending t, for each t (+w_t, y_i) then
+      (-w_t, y_j).  A void sample contributes (+-0, y_i).
+    - Item half, row i: first the samples whose positive is i, in ascending t,
+      with (+w_t, x_u).  Then the non-void samples whose negative is i, in
+      ascending t, with (-w_t, x_u).
+    - Each half then runs, in fp32, per row:
+
+        a = 0;  a = fma(val_e, row_e, a) over the entries in that order;   sv = sum of val_e
+        g = fma(-reg, x, a);  h = fma(g, g, h);  x += lr g / sqrt(1e-6 + h)
+        item half only:  gb = sv;  hb = fma(gb, gb, hb);  b += lr gb / sqrt(1e-6 + hb)      (bias not regularised, as in LMF)
+
+    - The accumulators start at zero.
+    - For a fixed draw this is ascent on
+      sum_t ln sig(z_t) - (reg/2)(|X|^2 + |Y|^2) over non-void t.
+
+    Between the two kernels (pinsage_bpr_sample, pinsage_bpr_apply) the entry
+    arrays are plain torch: the user half's have a fixed structure (its ptr is
+    R's times 2 S), the item half's CSR is built per iteration by one stable
+    sort of cat(positive item of t, neg[valid]).
+
+    Randomness.  The Philox seed is ``random_state`` or, with None, one
+    ``torch.randint(0, 2**63 - 1, (1,))`` from torch's global generator, drawn
+    before the tables.  Initial tables as LMF's: (torch.rand(n, f) - 0.5) / f,
+    users first, then items; the bias and the accumulators start at zero."""
+
+    _who = "BPR"
+
+    def __init__(self, factors=128, learning_rate=0.05, regularization=0.01, iterations=100, negatives=1,
+                 random_state=None):
+        super().__init__(factors, random_state)
+        if not (0 <= regularization < float("inf") and 0 <= learning_rate < float("inf") and int(iterations) >= 0):
+            raise ValueError("BPR: need finite regularization >= 0, learning_rate >= 0, iterations >= 0")
+        if not (negatives == int(negatives) and 1 <= int(negatives) <= BPR_MAX_NEGATIVES):
+            raise ValueError(f"BPR: negatives = {negatives}: need an integer in [1, {BPR_MAX_NEGATIVES}]")
+        if 2 * int(iterations) >= 1 << 27:
+            raise ValueError("BPR: draw round 2 * iterations must stay below 2^27")
+        self.learning_rate, self.regularization = float(learning_rate), float(regularization)
+        self.iterations, self.negatives = int(iterations), int(negatives)
+        self.item_bias = None
+
+    def _sample(self, rho, X, Y, b, err):
+        ptr, idx, _, n_users, n_items = self._user_items
+        f, S = self.factors, self.negatives
+        neg = torch.empty(int(idx.numel()) * S, dtype=torch.int32, device="cuda")
+        w = torch.empty(int(idx.numel()) * S, dtype=torch.float32, device="cuda")
+        nat.check(nat.lib().pinsage_bpr_sample(nat.ptr(ptr), nat.ptr(idx), n_users, 0, nat.ptr(X), f, nat.ptr(Y),
+                                               nat.ptr(b), n_items, f, f, S, self._seed, int(rho), 0, nat.ptr(neg),
+                                               nat.ptr(w), nat.ptr(err), nat.stream_ptr()), "bpr_sample")
+        return neg, w
+
+    def _apply(self, ptr, idx, val, n_rows, Y, n_other, X, bx, H, hb, err):
+        f = self.factors
+        nat.check(nat.lib().pinsage_bpr_apply(nat.ptr(ptr), nat.ptr(idx), nat.ptr(val), n_rows, nat.ptr(Y), n_other, f,
+                                              nat.ptr(X), nat.ptr(bx), f, f, nat.ptr(H), f, nat.ptr(hb),
+                                              self.regularization,
+                                              self.learning_rate, nat.ptr(err), nat.stream_ptr()), "bpr_apply")
+
+    def sample(self, rho):
+        """(neg int32 [nnz * negatives], w float32 [nnz * negatives]) on the GPU:
+        draw round rho against the current tables (pinsage_bpr_sample)."""
+        return self._sample(rho, self.user_factors, self.item_factors, self.item_bias,
+                            torch.zeros(1, dtype=torch.int32, device="cuda"))
+
+    def fit(self, user_items, user_factors=None, item_factors=None, item_bias=None, callback=None):
+        """user_items: the (ptr, idx, val, n_users, n_items) CSR.  Values are
+        checked once on the host to be finite and > 0 (ValueError) and rows to be
+        strictly ascending (ValueError); a column id outside [0, n_items) raises
+        IndexError.  Given factor and bias tables are copied, not written.
+        ``callback(iteration, self)`` runs after every iteration, the three
+        tables set (monitoring)."""
+        nat.require_gpu()
+        if self.random_state is None:
+            seed = int(torch.randint(0, 2 ** 63 - 1, (1,)))
+        else:
+            seed = int(self.random_state) & (2 ** 64 - 1)
+        csr_u, _, X, Y, err = self._intake(user_items, user_factors, item_factors)
+        ptr, idx, _, n_users, n_items = csr_u
+        rows = _csr_rows(ptr)
+        if int(ptr[0]) != 0 or int(ptr[-1]) != int(idx.numel()) or bool((ptr[1:] < ptr[:-1]).any()):
+            raise ValueError("BPR: the CSR arrays do not fit together")
+        if bool(((idx[1:] <= idx[:-1]) & (rows[1:] == rows[:-1])).any()):
+            raise ValueError("BPR: rows must be strictly ascending (the negative draw binary-searches the row)")
+        b = self._bias(item_bias, n_items)
+        self._seed = seed
+        S = self.negatives
+        Hx, Hy, hb = torch.zeros_like(X), torch.zeros_like(Y), torch.zeros_like(b)
+        pos = idx.to(torch.int64).clamp(0, n_items - 1).repeat_interleave(S)  # positive item of sample t
+        usr = rows.repeat_interleave(S).to(torch.int32)                       # user of sample t
+        ptr_u = ptr * (2 * S)
+        state = {"it": 0}
+
+        def user_half():
+            neg, w = self._sample(2 * state["it"], X, Y, b, err)
+            j = torch.where(neg >= 0, neg.to(torch.int64), pos)
+            self._apply(ptr_u, torch.stack([pos, j], 1).to(torch.int32).contiguous(),
+                        torch.stack([w, -w], 1).contiguous(), n_users, Y, n_items, X, None, Hx, None, err)
+
+        def item_half():
+            neg, w = self._sample(2 * state["it"] + 1, X, Y, b, err)
+            ok = neg >= 0
+            key = torch.cat([pos, neg[ok].to(torch.int64)])
+            order = torch.sort(key, stable=True).indices
+            self._apply(_csr_ptr(key, n_items), torch.cat([usr, usr[ok]])[order].contiguous(),
+                        torch.cat([w, -w[ok]])[order].contiguous(), n_items, X, n_users, Y, b, Hy, hb, err)
+            state["it"] += 1
+
+        return self._iterate(user_half, item_half, err, {"user_factors": X, "item_factors": Y, "item_bias": b},
+                             callback)
+
+    def objective(self, neg=None):
+        """bpr_objective of the fitted tables on the draw ``neg`` (a Python float;
+        monitoring and tests).  By default the draw of round 2 * iterations,
+        which the fit never uses."""
+        if neg is None:
+            neg = self.sample(2 * self.iterations)[0]
+        return bpr_objective(self._user_items, self.user_factors, self.item_factors, self.item_bias, neg,
+                             self.negatives, self.regularization)
+
+
 class _CfModel(PredictionModel):
-    """A factorisation baseline: ``train`` fits a ``_Fit`` (ALS or LMF) to the
+    """A factorisation baseline: ``train`` fits a ``_Fit`` (ALS, LMF or BPR) to the
     ``_matrix`` of the training data and leaves it in ``self.model``."""
 
     def train(self, g, ids, train_set, test_set, features):
@@ -1067,7 +1263,7 @@ class _CfALS(_CfModel):
     def __init__(self, algo="als", factors=128):
         if algo != "als":  # the reference's "lmf" and "bpr" come from implicit too
             raise NotImplementedError(f"algo = {algo!r}: ALS ('als') is the only algorithm of these classes; "
-                                      "logistic MF is ColTrackLMF / TrackTrackLMF")
+                                      "logistic MF is ColTrackLMF / TrackTrackLMF, BPR is ColTrackBPR / TrackTrackBPR")
         self.algo = algo
         self.factors = factors
 
@@ -1077,6 +1273,14 @@ class _CfLMF(_CfModel):
 
     def __init__(self, factors=128):
         self.algo = "lmf"
+        self.factors = factors
+
+
+class _CfBPR(_CfModel):
+    _Fit = BPR
+
+    def __init__(self, factors=128):
+        self.algo = "bpr"
         self.factors = factors
 
 
@@ -1108,6 +1312,17 @@ class TrackTrackLMF(_TrackTrack, _CfLMF):
 class ColTrackLMF(_ColTrack, _CfLMF):
     """ColTrackCF with the fit replaced by logistic matrix factorisation
     (the reference's algo="lmf"; ``LMF`` above)."""
+
+
+class TrackTrackBPR(_TrackTrack, _CfBPR):
+    """TrackTrackCF with the fit replaced by Bayesian personalised ranking
+    (the reference's algo="bpr"; ``BPR`` above).  The counts of the track-track
+    matrix are not used: every stored cell is one positive."""
+
+
+class ColTrackBPR(_ColTrack, _CfBPR):
+    """ColTrackCF with the fit replaced by Bayesian personalised ranking
+    (the reference's algo="bpr"; ``BPR`` above)."""
 
 
 # ----------------------------------------------------------------------------- node2vec
@@ -1481,4 +1696,5 @@ __all__ = ["PRECOMP_K", "PredictionModel", "EmbeddingModel", "cosine_sim_ab", "k
            "compute_results_table", "ALS_MAX_FACTORS", "ALS", "als_loss", "to_col_track_matrix",
            "to_track_track_matrix", "ColTrackCF", "TrackTrackCF", "LMF_MAX_FACTORS", "LMF", "lmf_objective",
            "ColTrackLMF", "TrackTrackLMF", "project_bipartite_graph", "bipartite_graph", "n2v_cooccurrence",
-           "sgns_objective", "N2V_MAX_BIAS_RATIO", "Node2Vec", "FastNode2Vec"]
+           "sgns_objective", "N2V_MAX_BIAS_RATIO", "Node2Vec", "FastNode2Vec", "BPR_MAX_FACTORS", "BPR_MAX_TRIES",
+           "BPR_MAX_NEGATIVES", "BPR", "bpr_objective", "ColTrackBPR", "TrackTrackBPR"]

@@ -10,6 +10,7 @@
 #include "../../include/pinsage_hip.h"
 #include "aggw.h"
 #include "als.h"
+#include "bpr.h"
 #include "lmf.h"
 #include "n2v.h"
 #include "capi.h"
@@ -789,6 +790,23 @@ int pinsage_lmf_update(const int64_t* ptr, const int32_t* idx, const float* val,
                        float alpha, float reg, float lr, int* err, void* stream) {
   return launch_lmf_update(ptr, idx, val, n_rows, Y, by, n_other, ldy, X, bx, ldx, f, D, ldd, dsum, H, ldh, hb,
                            alpha, reg, lr, err, (hipStream_t)stream);
+}
+
+int64_t pinsage_bpr_max_tries(void) { return bpr_max_tries(); }
+
+int pinsage_bpr_sample(const int64_t* ptr, const int32_t* idx, int64_t n_rows, int64_t cell_base, const float* X,
+                       int64_t ldx, const float* Y, const float* by, int64_t n_other, int64_t ldy, int64_t f,
+                       int64_t negatives, uint64_t seed, int64_t rho, uint32_t offset, int32_t* neg, float* w, int* err,
+                       void* stream) {
+  return launch_bpr_sample(ptr, idx, n_rows, cell_base, X, ldx, Y, by, n_other, ldy, f, negatives, seed, rho, offset,
+                           neg, w, err, (hipStream_t)stream);
+}
+
+int pinsage_bpr_apply(const int64_t* ptr, const int32_t* idx, const float* val, int64_t n_rows, const float* Y,
+                      int64_t n_other, int64_t ldy, float* X, float* bx, int64_t ldx, int64_t f, float* H, int64_t ldh,
+                      float* hb, float reg, float lr, int* err, void* stream) {
+  return launch_bpr_apply(ptr, idx, val, n_rows, Y, n_other, ldy, X, bx, ldx, f, H, ldh, hb, reg, lr, err,
+                          (hipStream_t)stream);
 }
 
 int pinsage_n2v_walk(const int64_t* ptr, const int32_t* idx, const int64_t* cum, int64_t n_nodes,

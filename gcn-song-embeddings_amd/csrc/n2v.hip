@@ -37,18 +37,6 @@ struct N2vArgs {
   int* err;
 };
 
-// whether node v is in the ascending row [b, e) of idx
-__device__ __forceinline__ bool n2v_in_row(const int32_t* __restrict__ idx, int64_t b, int64_t e, int32_t v) {
-  while (b < e) {
-    const int64_t m = b + ((e - b) >> 1);
-    const int32_t a = idx[m];
-    if (a == v) return true;
-    if (a < v) b = m + 1;
-    else e = m;
-  }
-  return false;
-}
-
 __global__ __launch_bounds__(kN2vBlock) void n2v_walk_kernel(N2vArgs A) {
   const int64_t k = (int64_t)blockIdx.x * kN2vBlock + threadIdx.x;
   if (k >= A.n_walks) return;
@@ -89,7 +77,7 @@ __global__ __launch_bounds__(kN2vBlock) void n2v_walk_kernel(N2vArgs A) {
         cand = 0;
       }
       if (j == 1) break;
-      const float beta = cand == prev ? A.inv_p : (n2v_in_row(A.idx, pb, pe, (int32_t)cand) ? 1.f : A.inv_q);
+      const float beta = cand == prev ? A.inv_p : (row_holds(A.idx, pb, pe, (int32_t)cand) ? 1.f : A.inv_q);
       const float u = (float)(r.z >> 8) * 0x1p-24f;  // exact
       if (u * A.M < beta) break;
     }

@@ -1,5 +1,6 @@
-// The row plan of the row-wise fits' two kernels (als_half_kernel in als.hip,
-// sig_update_kernel in sig_update.h for lmf.hip and n2v.hip): a workgroup of kRowWaves
+// The row plan of the row-wise fits' kernels (als_half_kernel in als.hip,
+// sig_update_kernel in sig_update.h for lmf.hip and n2v.hip, the two kernels of
+// bpr.hip): a workgroup of kRowWaves
 // waves owns a block of kRowWaves consecutive CSR rows.  A lane owns columns
 // 2 lane and 2 lane + 1 of every f-vector, so a gathered row of Y is one 8-byte
 // load per lane.  An ordinary row (at most kRowLong items) is one wave's, its
@@ -33,6 +34,18 @@ struct RowItems {
 
 __device__ __forceinline__ float2 row_ld2(const float* p, bool on) {
   return on ? *reinterpret_cast<const float2*>(p) : make_float2(0.f, 0.f);
+}
+
+// whether id v is in the ascending row [b, e) of idx
+__device__ __forceinline__ bool row_holds(const int32_t* __restrict__ idx, int64_t b, int64_t e, int32_t v) {
+  while (b < e) {
+    const int64_t m = b + ((e - b) >> 1);
+    const int32_t a = idx[m];
+    if (a == v) return true;
+    if (a < v) b = m + 1;
+    else e = m;
+  }
+  return false;
 }
 
 // The items [b, e) in groups of 64 (group g0, g0 + gs, ...), in order:

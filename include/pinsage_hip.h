@@ -988,6 +988,79 @@ int pinsage_sgns_update(const int64_t* ptr, const int32_t* idx, const float* val
                         const float* Y, int64_t n_other, int64_t ldy, float* X, int64_t ldx, int64_t f, const float* D,
                         int64_t ldd, float* H, int64_t ldh, float reg, float lr, int* err, void* stream);
 
+/* ------------------------------------------------------------------ Bayesian personalised ranking
+ * Rendle, Freudenthaler, Gantner, Schmidt-Thieme, "BPR: Bayesian Personalized
+ * Ranking from Implicit Feedback" (2009), as this project defines it: the
+ * algo="bpr" the reference takes from the implicit package, with the negatives
+ * from a counter-based generator and Jacobi AdaGrad half-iterations in place of
+ * that package's sampled SGD with racing updates.  Deterministic; parity with
+ * that package's numbers is not claimed.
+ *
+ * Inputs and tables.  R [n_users, n_items] is a CSR whose rows are strictly
+ * ascending; only its structure is used, every stored cell is one positive.
+ * Tables X [n_users, f], Y [n_items, f] and an item bias b [n_items]; there is
+ * no user bias.  Cell e is the e-th stored cell of R; sample t = e * S + s for
+ * s < S = negatives.
+ *
+ * The draw.  For draw round rho, sample t of a cell (u, i), and tries k = 0 .. 15:
+ *   (r0, r1, r2, r3) = Philox4x32-10(key = seed, ctr = (rho * 16 + k, t lo, t hi, offset))
+ *   j = (uint64(r0) * n_items) >> 32
+ *   accept the first j that is not a column of row u   (binary search; j == i is therefore rejected)
+ * After 16 rejected tries the sample is void: neg[t] = -1, w[t] = 0.  Otherwise
+ * neg[t] = j and, with z = (x_u . y_i + b_i) - (x_u . y_j + b_j), w[t] = sig(-z).
+ * The dot is the row plan's: two columns per lane, fmaf(x.x, y.x, x.y * y.y),
+ * then the wave sum.  The sigmoid is that of logistic MF above.  neg and w of
+ * sample t depend on (seed, rho, offset, t, row u, the tables) only; they do not
+ * depend on the grid or on batching.
+ *
+ * One iteration `it`.  The user half uses draw round 2 it; the item half uses
+ * round 2 it + 1 and the new X.  Both halves are Jacobi.
+ *   User half, row u, entries in ascending t, for each t (+w_t, y_i) then
+ *   (-w_t, y_j).  A void sample contributes (+-0, y_i).
+ *   Item half, row i: first the samples whose positive is i, in ascending t,
+ *   with (+w_t, x_u); then the non-void samples whose negative is i, in
+ *   ascending t, with (-w_t, x_u).
+ * Each half then runs, in fp32, per row:
+ *   a = 0;  a = fma(val_e, row_e, a) over the entries in that order;   sv = sum of val_e
+ *   g = fma(-reg, x, a);  h = fma(g, g, h);  x += lr g / sqrt(1e-6 + h)
+ *   item half only:  gb = sv;  hb = fma(gb, gb, hb);  b += lr gb / sqrt(1e-6 + hb)      (bias not regularised, as in LMF)
+ * The accumulators start at zero.  For a fixed draw this is ascent on
+ * sum_t ln sig(z_t) - (reg/2)(|X|^2 + |Y|^2) over non-void t.
+ *
+ * pinsage_bpr_sample: neg int32 [nnz negatives] and w f32 [nnz negatives] for
+ * every row of the CSR (ptr int64 [n_rows + 1] from 0, idx int32) against X f32
+ * [n_rows][ldx], Y f32 [n_other][ldy], by f32 [n_other]; no table is written.
+ * The call's cell e is cell cell_base + e of R: a block of rows handed over
+ * alone (ptr rebased to 0, its idx, its rows of X, its outputs) draws what it
+ * draws in the whole matrix.  One wave per row of at most
+ * pinsage_lmf_long_row() cells, the workgroup for a longer one; samples are
+ * independent and nothing is reduced.  pinsage_bpr_max_tries() is the 16 above.
+ * A positive id outside [0, n_other) sets *err and is clamped to 0.  Refused
+ * (PINSAGE_ERR_ARG, nothing launched, outputs untouched): f, leading dimensions
+ * and alignment as the logistic MF pair; a null ptr or by; negatives outside
+ * [1, 8]; rho outside [0, 2^27); cell_base < 0; a count above INT32_MAX;
+ * n_other < 1.  n_rows == 0 is accepted and launches nothing.
+ *
+ * pinsage_bpr_apply: the signed gathered row sum and the AdaGrad step, in place
+ * on X, H f32 [n_rows][ldh] and, unless both are null (the user half), bx and hb
+ * f32 [n_rows], for a CSR (ptr, idx int32 in [0, n_other), val f32 of either
+ * sign) against Y f32 [n_other][ldy].  sv is summed in CSR order from 0.  Row
+ * forms as pinsage_lmf_update: a long row's partial sums of a and sv are added
+ * in wave order.  lr == 0 leaves X and bx bit for bit and still updates H and
+ * hb.  A row without entries and with reg = 0 keeps x exactly.  err as
+ * pinsage_als_half.  Refused: f, leading dimensions, alignment and null tables
+ * as the logistic MF pair; a null ptr; exactly one of bx, hb null; reg < 0,
+ * lr < 0 or either not finite; a count above INT32_MAX; n_other < 1.
+ * n_rows == 0 is accepted and launches nothing. */
+int64_t pinsage_bpr_max_tries(void);
+int pinsage_bpr_sample(const int64_t* ptr, const int32_t* idx, int64_t n_rows, int64_t cell_base, const float* X,
+                       int64_t ldx, const float* Y, const float* by, int64_t n_other, int64_t ldy, int64_t f,
+                       int64_t negatives, uint64_t seed, int64_t rho, uint32_t offset, int32_t* neg, float* w, int* err,
+                       void* stream);
+int pinsage_bpr_apply(const int64_t* ptr, const int32_t* idx, const float* val, int64_t n_rows, const float* Y,
+                      int64_t n_other, int64_t ldy, float* X, float* bx, int64_t ldx, int64_t f, float* H, int64_t ldh,
+                      float* hb, float reg, float lr, int* err, void* stream);
+
 /* ------------------------------------------------------------------ train-step engine
  * PinSageModel.forward / PinSage.train_batch (pinsage_model.py:246-265,
  * pinsage_training.py:181-214) with device-resident sizes.  Parameters live in
