@@ -183,6 +183,11 @@ _SIGS = {
     "pinsage_cooc_scratch_bytes": (i64, [i64, i64]),
     "pinsage_cooc_counts": (ctypes.c_int, [vp, vp, vp, vp, i64, i64, vp, i64, vp, vp, vp]),
     "pinsage_cooc_jaccard": (ctypes.c_int, [vp, vp, vp, vp, i64, i64, vp, i64, i64, vp, i64, vp, vp, vp, vp]),
+    "pinsage_cooc_weighted_tile": (i64, []),
+    "pinsage_cooc_weighted_scratch_bytes": (i64, [i64, i64]),
+    "pinsage_cooc_weighted_sums": (ctypes.c_int, [vp, vp, vp, vp, i64, i64, vp, vp, i64, vp, vp, vp]),
+    "pinsage_cooc_weighted_knn": (ctypes.c_int, [vp, vp, vp, vp, i64, i64, vp, vp, i64, i64, vp, i64, vp, vp, vp,
+                                                 vp]),
     "pinsage_als_rows_per_block": (i64, []),
     "pinsage_als_long_row": (i64, []),
     "pinsage_als_gram": (ctypes.c_int, [vp, i64, i64, i64, f32, vp, vp]),

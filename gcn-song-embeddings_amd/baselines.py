@@ -44,7 +44,16 @@ the walks' window co-occurrence counts that runs on the LMF scaffold
 kernel and a sparse update).  Again this package's own definition,
 deterministic, with no parity with fastnode2vec or gensim claimed.
 
-The reference's other baseline recommenders (networkx similarities, lib/gnns)
+``SimpleSimilarity`` and its ``JaccardIndex`` / ``AdamicAdar`` /
+``Preferential`` (baselines.py:153-191, one networkx call per pair there) score
+a query against all tracks at once: Adamic-Adar on the weighted form of the
+count kernel (64-bit fixed-point sums, csrc/cooc.hip) and the selection kernel
+under a score key, the Jaccard coefficient on the Jaccard path above, and
+preferential attachment from one sort of the degrees.  ``JaccardIndex`` computes
+the Jaccard coefficient, not the preferential attachment the reference assigns
+to that name.
+
+The reference's other baseline recommenders (lib/gnns)
 and implicit's own sampled-SGD order for bpr are out of scope; their libraries are not part of this
 build.  Names, signatures, return types and RNG consumption
 follow the reference; compute runs in HIP (no CPU fallback).
@@ -626,6 +635,34 @@ def _membership_csrs(g, n_tracks, who):
     return t2c, c2t, n_cols
 
 
+def _track_queries(nodeset, n, who):
+    """nodeset as contiguous int64 query ids on the GPU; IndexError outside [0, n)."""
+    qs = torch.as_tensor(nodeset).reshape(-1).to(torch.int64)
+    if qs.numel() and (int(qs.min()) < 0 or int(qs.max()) >= n):
+        raise IndexError(f"{who}: query ids out of range for {n} tracks")
+    return qs.to("cuda").contiguous()
+
+
+def _cooc_lists(entry, scratch_bytes, csr_args, n, qd, k, who):
+    """The k best of each query under one of the list entries of csrc/cooc.hip
+    (pinsage_cooc_jaccard / pinsage_cooc_weighted_knn; csr_args ends where the
+    queries begin): (float32 [nq, k], int64 [nq, k]) on the GPU, sorted (score
+    descending, id ascending)."""
+    nq, k = int(qd.numel()), int(k)
+    w = torch.empty((nq, k), dtype=torch.float32, device="cuda")
+    nb = torch.empty((nq, k), dtype=torch.int64, device="cuda")
+    if nq:
+        L = nat.lib()
+        nbytes = getattr(L, scratch_bytes)(n, _batch_rows(nq, n))
+        scratch = torch.empty(nbytes, dtype=torch.uint8, device="cuda")
+        err = torch.zeros(1, dtype=torch.int32, device="cuda")
+        nat.check(getattr(L, entry)(*csr_args, nat.ptr(qd), nq, k, nat.ptr(scratch), nbytes, nat.ptr(w), nat.ptr(nb),
+                                    nat.ptr(err), nat.stream_ptr()), entry[len("pinsage_"):])
+        if int(err):
+            raise IndexError(f"{who}: query ids out of range for {n} tracks")
+    return w, nb
+
+
 class JaccardFast(PredictionModel):
     """Nearest neighbours by the Jaccard similarity of the tracks' collection
     sets (baselines.py:194-220):  |C(q) & C(t)| / (|C(q) | C(t)| + 1e-10).
@@ -663,10 +700,7 @@ class JaccardFast(PredictionModel):
         self.nbh_sizes = self._t2c[0][1:] - self._t2c[0][:-1]  # int64 [n_tracks], on the GPU
 
     def _queries(self, nodeset):
-        qs = torch.as_tensor(nodeset).reshape(-1).to(torch.int64)
-        if qs.numel() and (int(qs.min()) < 0 or int(qs.max()) >= self.n):
-            raise IndexError(f"JaccardFast: query ids out of range for {self.n} tracks")
-        return qs.to("cuda").contiguous()
+        return _track_queries(nodeset, self.n, "JaccardFast")
 
     def _csr_args(self):
         return (nat.ptr(self._t2c[0]), nat.ptr(self._t2c[1]), nat.ptr(self._c2t[0]), nat.ptr(self._c2t[1]),
@@ -690,20 +724,8 @@ class JaccardFast(PredictionModel):
         (float32 [nq, k - 1], int64 [nq, k - 1]) on nodeset's device, k - 1
         columns (not k, as knn_from_emb returns)."""
         out_dev = torch.as_tensor(nodeset).device
-        qd = self._queries(nodeset)
-        nq, k, n = int(qd.numel()), int(k), self.n
-        w = torch.empty((nq, k), dtype=torch.float32, device="cuda")
-        nb = torch.empty((nq, k), dtype=torch.int64, device="cuda")
-        if nq:
-            L = nat.lib()
-            nbytes = L.pinsage_cooc_scratch_bytes(n, _batch_rows(nq, n))
-            scratch = torch.empty(nbytes, dtype=torch.uint8, device="cuda")
-            err = torch.zeros(1, dtype=torch.int32, device="cuda")
-            nat.check(L.pinsage_cooc_jaccard(*self._csr_args(), nat.ptr(qd), nq, k, nat.ptr(scratch), nbytes,
-                                             nat.ptr(w), nat.ptr(nb), nat.ptr(err), nat.stream_ptr()),
-                      "cooc_jaccard")
-            if int(err):
-                raise IndexError(f"JaccardFast: query ids out of range for {n} tracks")
+        w, nb = _cooc_lists("pinsage_cooc_jaccard", "pinsage_cooc_scratch_bytes", self._csr_args(), self.n,
+                            self._queries(nodeset), k, "JaccardFast")
         return w[:, 1:].to(out_dev), nb[:, 1:].to(out_dev)
 
 
@@ -1625,6 +1647,142 @@ class FastNode2Vec(EmbeddingModel):
         return knn_from_emb(self.embedding, nodeset, k)
 
 
+# ----------------------------------------------------------------------------- link-prediction indices
+# baselines.py:153-191.  Two-hop scores between tracks over a graph held as the
+# two CSRs of csrc/cooc.hip: t2c, n rows of middle ids in [0, n_mid), and c2t,
+# n_mid rows of track ids, both ascending and without duplicates.
+#   deg(t) = len(t2c row t),  dmid(c) = len(c2t row c),  cn(q, t) = |N(q) & N(t)|
+LINKSIM_SHIFT = 30  # fixed point of the Adamic-Adar weights (kCoocShift, csrc/cooc.hip)
+
+
+def adamic_adar_weights(dmid):
+    """The fixed-point weight of a middle node of each degree in ``dmid``:
+    floor(2^30 / ln(d) + 0.5) as int64, formed in float64 on dmid's device, and 0
+    for d <= 1 (such a node joins no two distinct tracks).  With 2^30 a sum over
+    fewer than 2^31 middle nodes stays below 2^62."""
+    d = torch.as_tensor(dmid).to(torch.float64)
+    w = torch.floor(float(1 << LINKSIM_SHIFT) / torch.log(d.clamp(min=2.0)) + 0.5)
+    return torch.where(d >= 2, w, torch.zeros_like(w)).to(torch.int64)
+
+
+class SimpleSimilarity(PredictionModel):
+    """Base of the three networkx link-prediction indices (baselines.py:153-174),
+    which the reference scores one pair at a time, n pairs per query, in Python.
+
+    ``projected=True``: the graph is the track-track projection
+    (``project_bipartite_graph``; its weights are ignored, as networkx's three
+    functions ignore them), so both CSRs are its adjacency and the middle nodes
+    are tracks.  ``projected=False``: the bipartite graph, the middle nodes are
+    the collections, membership is JaccardFast.train's rule.  That rule drops an
+    edge between two tracks, which networkx would keep as an edge of the graph.
+
+    ``knn(nodeset, k)`` is the reference's bare ``topk(k)`` of the query's score
+    row against all tracks: k columns, column 0 NOT dropped (it is the query
+    itself only where nothing ties or beats it), on nodeset's device, in this
+    package's order (score descending, then id ascending)."""
+
+    def __init__(self, projected=True):
+        self.projected = projected
+
+    def train(self, g, ids, train_set, test_set, features):
+        nat.require_gpu()
+        who = type(self).__name__
+        self.ids = ids
+        self.n = n = len(ids)
+        if self.projected:
+            ptr, idx, _, _ = project_bipartite_graph(g, ids)
+            self._t2c = self._c2t = (ptr, idx)
+            self.n_mid = n
+        else:
+            self._t2c, self._c2t, self.n_mid = _membership_csrs(g, n, who)
+        self.deg = self._t2c[0][1:] - self._t2c[0][:-1]    # int64 [n], on the GPU
+        self.dmid = self._c2t[0][1:] - self._c2t[0][:-1]   # int64 [n_mid]
+
+    def _queries(self, nodeset):
+        return _track_queries(nodeset, self.n, type(self).__name__)
+
+    def _csr_args(self):
+        return (nat.ptr(self._t2c[0]), nat.ptr(self._t2c[1]), nat.ptr(self._c2t[0]), nat.ptr(self._c2t[1]),
+                self.n, self.n_mid)
+
+
+class JaccardIndex(SimpleSimilarity):
+    """The Jaccard coefficient of two tracks' neighbour sets,
+    cn / (deg q + deg t - cn), 0 where the union is empty: networkx's
+    ``jaccard_coefficient``.  The reference's class of this name is assigned
+    ``nx.preferential_attachment`` (baselines.py:176-180), evidently by mistake;
+    this one computes what the name says.  No kernel of its own: it is
+    pinsage_cooc_jaccard over the model's CSRs, whose fp32 co / (union + 1e-10)
+    equals float32 of networkx's value bit for bit for degrees below 2^24.  With
+    projected=False, ``knn(q, k)[:, 1:]`` is ``JaccardFast.knn(q, k)``."""
+
+    def knn(self, nodeset, k):
+        out_dev = torch.as_tensor(nodeset).device
+        w, nb = _cooc_lists("pinsage_cooc_jaccard", "pinsage_cooc_scratch_bytes", self._csr_args(), self.n,
+                            self._queries(nodeset), k, "JaccardIndex")
+        return w.to(out_dev), nb.to(out_dev)
+
+
+class AdamicAdar(SimpleSimilarity):
+    """The Adamic-Adar index, the sum over the common neighbours c of
+    1 / ln dmid(c), in fixed point (csrc/cooc.hip's weighted kernel):
+
+        wt = adamic_adar_weights(dmid);  S(q, t) = sum of wt[c], int64
+        score = float32(S) * 2^-30       (int64 -> float32 to nearest even)
+
+    Integer adds make S, and so the lists, independent of the order of the
+    adds.  networkx raises ZeroDivisionError on the pair (q, q) where q has a
+    neighbour of degree 1 (ln 1 = 0); such a neighbour weighs 0 here."""
+
+    def train(self, g, ids, train_set, test_set, features):
+        super().train(g, ids, train_set, test_set, features)
+        # on the host: one table, whatever the device's log rounds to
+        self.weights = adamic_adar_weights(self.dmid.cpu()).to("cuda").contiguous()
+
+    def _weighted_args(self):
+        return self._csr_args() + (nat.ptr(self.weights),)
+
+    def sums(self, nodeset):
+        """S(q, .) of each query, dense: int64 [len(nodeset), n] on the GPU."""
+        qd = self._queries(nodeset)
+        nq = int(qd.numel())
+        out = torch.empty((nq, self.n), dtype=torch.int64, device="cuda")
+        err = torch.zeros(1, dtype=torch.int32, device="cuda")
+        nat.check(nat.lib().pinsage_cooc_weighted_sums(*self._weighted_args(), nat.ptr(qd), nq, nat.ptr(out),
+                                                       nat.ptr(err), nat.stream_ptr()), "cooc_weighted_sums")
+        if int(err):
+            raise IndexError(f"AdamicAdar: query ids out of range for {self.n} tracks")
+        return out
+
+    def knn(self, nodeset, k):
+        out_dev = torch.as_tensor(nodeset).device
+        w, nb = _cooc_lists("pinsage_cooc_weighted_knn", "pinsage_cooc_weighted_scratch_bytes",
+                            self._weighted_args(), self.n, self._queries(nodeset), k, "AdamicAdar")
+        return w.to(out_dev), nb.to(out_dev)
+
+
+class Preferential(SimpleSimilarity):
+    """Preferential attachment, deg(q) deg(t), exact in int64 (the reference's
+    ``torch.tensor`` of Python ints is int64 too).  For deg(q) > 0 the order
+    (score descending, id ascending) is deg(t) descending, then id ascending,
+    whatever the query: one stable sort at ``train``, and ``knn`` is its first k
+    ids with the products as weights.  For deg(q) = 0 every score is 0: ids
+    0 .. k - 1, weights zeros.  Plain torch on the GPU; no kernel."""
+
+    def train(self, g, ids, train_set, test_set, features):
+        super().train(g, ids, train_set, test_set, features)
+        self._by_degree = torch.sort(self.deg, descending=True, stable=True).indices
+
+    def knn(self, nodeset, k):
+        out_dev = torch.as_tensor(nodeset).device
+        qd, k = self._queries(nodeset), int(k)
+        if not 0 <= k <= self.n:
+            raise ValueError(f"Preferential: k = {k} over {self.n} tracks")
+        dq = self.deg[qd].unsqueeze(1)
+        nb = torch.where(dq > 0, self._by_degree[:k].unsqueeze(0), torch.arange(k, device="cuda").unsqueeze(0))
+        return (dq * self.deg[nb]).to(out_dev), nb.to(out_dev)
+
+
 class Random(PredictionModel):
     """Random recommendations (baselines.py:380-397): per query the first k of
     a ``torch.randperm(n)`` from torch's global generator, weights of ones (int64,
@@ -1697,4 +1855,5 @@ __all__ = ["PRECOMP_K", "PredictionModel", "EmbeddingModel", "cosine_sim_ab", "k
            "to_track_track_matrix", "ColTrackCF", "TrackTrackCF", "LMF_MAX_FACTORS", "LMF", "lmf_objective",
            "ColTrackLMF", "TrackTrackLMF", "project_bipartite_graph", "bipartite_graph", "n2v_cooccurrence",
            "sgns_objective", "N2V_MAX_BIAS_RATIO", "Node2Vec", "FastNode2Vec", "BPR_MAX_FACTORS", "BPR_MAX_TRIES",
-           "BPR_MAX_NEGATIVES", "BPR", "bpr_objective", "ColTrackBPR", "TrackTrackBPR"]
+           "BPR_MAX_NEGATIVES", "BPR", "bpr_objective", "ColTrackBPR", "TrackTrackBPR", "LINKSIM_SHIFT",
+           "adamic_adar_weights", "SimpleSimilarity", "JaccardIndex", "AdamicAdar", "Preferential"]

@@ -760,6 +760,27 @@ int pinsage_cooc_jaccard(const int64_t* t2c_ptr, const int32_t* t2c_idx, const i
                              scratch_bytes, out_w, out_n, err, (hipStream_t)stream);
 }
 
+int64_t pinsage_cooc_weighted_tile(void) { return cooc_weighted_tile(); }
+
+int64_t pinsage_cooc_weighted_scratch_bytes(int64_t n_tracks, int64_t batch_rows) {
+  return cooc_weighted_scratch_bytes(n_tracks, batch_rows < 1 ? 1 : batch_rows);
+}
+
+int pinsage_cooc_weighted_sums(const int64_t* t2c_ptr, const int32_t* t2c_idx, const int64_t* c2t_ptr,
+                               const int32_t* c2t_idx, int64_t n_tracks, int64_t n_cols, const int64_t* wt,
+                               const int64_t* queries, int64_t nq, int64_t* out, int* err, void* stream) {
+  return launch_cooc_weighted_sums(t2c_ptr, t2c_idx, c2t_ptr, c2t_idx, n_tracks, n_cols, wt, queries, nq, out, err,
+                                   (hipStream_t)stream);
+}
+
+int pinsage_cooc_weighted_knn(const int64_t* t2c_ptr, const int32_t* t2c_idx, const int64_t* c2t_ptr,
+                              const int32_t* c2t_idx, int64_t n_tracks, int64_t n_cols, const int64_t* wt,
+                              const int64_t* queries, int64_t nq, int64_t k, void* scratch, int64_t scratch_bytes,
+                              float* out_w, int64_t* out_n, int* err, void* stream) {
+  return launch_cooc_weighted_knn(t2c_ptr, t2c_idx, c2t_ptr, c2t_idx, n_tracks, n_cols, wt, queries, nq, k, scratch,
+                                  scratch_bytes, out_w, out_n, err, (hipStream_t)stream);
+}
+
 int64_t pinsage_als_rows_per_block(void) { return als_rows_per_block(); }
 
 int64_t pinsage_als_long_row(void) { return als_long_row(); }

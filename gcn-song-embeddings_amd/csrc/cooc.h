@@ -36,4 +36,31 @@ int launch_cooc_jaccard(const int64_t* t2c_ptr, const int32_t* t2c_idx, const in
                         int64_t nq, int64_t k, void* scratch, int64_t scratch_bytes, float* out_w, int64_t* out_n,
                         int* err, hipStream_t st);
 
+// The weighted form: the same two CSRs read as node -> middle nodes and middle
+// node -> nodes (for a graph's own adjacency both are that adjacency), and
+// wt int64 [n_cols], a weight per middle node (null only where n_cols == 0):
+//   S(q, t) = sum of wt[c] over the middle nodes c that neighbour both q and t,
+// in 64-bit integer adds (wrapping), so two runs give the same bits.
+
+// 64-bit counters of one LDS tile of the weighted kernel (kCoocWTile)
+int cooc_weighted_tile();
+
+// scratch bytes of launch_cooc_weighted_knn for batches of qb query rows
+int64_t cooc_weighted_scratch_bytes(int64_t n_tracks, int64_t qb);
+
+// out int64 [nq][n_tracks]: out[i][t] = S(queries[i], t), every element written
+// exactly once; query ids as in launch_cooc_counts.
+int launch_cooc_weighted_sums(const int64_t* t2c_ptr, const int32_t* t2c_idx, const int64_t* c2t_ptr,
+                              const int32_t* c2t_idx, int64_t n_tracks, int64_t n_cols, const int64_t* wt,
+                              const int64_t* queries, int64_t nq, int64_t* out, int* err, hipStream_t st);
+
+// out_w / out_n [nq][k]: the k largest of float32(S) * 2^-30 (the int64 ->
+// float32 conversion rounds to nearest even) per query, sorted (score desc,
+// index asc), by launch_knn_select_score.  Arguments, batching and limits as
+// launch_cooc_jaccard; sums must be >= 0.
+int launch_cooc_weighted_knn(const int64_t* t2c_ptr, const int32_t* t2c_idx, const int64_t* c2t_ptr,
+                             const int32_t* c2t_idx, int64_t n_tracks, int64_t n_cols, const int64_t* wt,
+                             const int64_t* queries, int64_t nq, int64_t k, void* scratch, int64_t scratch_bytes,
+                             float* out_w, int64_t* out_n, int* err, hipStream_t st);
+
 }  // namespace ps

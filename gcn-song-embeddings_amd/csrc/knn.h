@@ -26,6 +26,13 @@ int knn_max_k();
 int launch_knn_select_jaccard(const int32_t* counts, int64_t n, const int32_t* deg, const int32_t* qdeg, int64_t m,
                               int64_t k, float* out_w, int64_t* out_n, hipStream_t st);
 
+// The same selection over finished scores: row b of scores float [m][n] holds
+// values >= 0 (no NaN); out_w / out_n [m][k]: the k largest, sorted (score desc,
+// index asc), out_w the scores' own bits.  scores must be 16-byte aligned when
+// n % 4 == 0; m <= 65535.
+int launch_knn_select_score(const float* scores, int64_t n, int64_t m, int64_t k, float* out_w, int64_t* out_n,
+                            hipStream_t st);
+
 // scratch bytes for rank batches of qb query rows over n table rows
 int64_t rank_scratch_bytes(int64_t n, int64_t qb);
 // most targets one query row may own (kRankMaxGroup)

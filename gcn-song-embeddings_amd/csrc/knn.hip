@@ -20,7 +20,8 @@
 //
 // The selection kernel is a template over a key policy (what a row holds and
 // how a key is made of it): cosine over dot products here, Jaccard over the
-// co-occurrence counts of cooc.hip (launch_knn_select_jaccard).
+// co-occurrence counts of cooc.hip (launch_knn_select_jaccard), finished scores
+// over its weighted sums (launch_knn_select_score).
 //
 // The ranks of given rows in that order (the positives of held-out pairs:
 // eval.py:227-250 hit_rate / mrr) are counted without any list by
@@ -81,6 +82,18 @@ struct KnnJaccardKey {
   __device__ __forceinline__ uint32_t operator()(int32_t co, int32_t dj, int32_t dq) const {
     return f2key((float)co / __fadd_rn((float)(dq + dj - co), 1e-10f));
   }
+};
+// A row of finished scores >= 0 (the weighted sums of cooc.hip as floats): the
+// key is the score's own image; the column value and the row scalar take no part.
+struct KnnScoreKey {
+  using Row = float;
+  using Row4 = float4;
+  using Col = float;
+  using Col4 = float4;
+  using Scalar = float;
+  static constexpr bool kFloor = true;
+  static constexpr uint32_t kFloorKey = 0x80000000u;  // f2key(0.0f)
+  __device__ __forceinline__ uint32_t operator()(float s, float, float) const { return f2key(s); }
 };
 
 __global__ void knn_row_norms_kernel(const float* __restrict__ e, int64_t n, int d, int64_t ld,
@@ -539,6 +552,22 @@ int launch_knn_select_jaccard(const int32_t* counts, int64_t n, const int32_t* d
   while (P < k) P <<= 1;
   hipLaunchKernelGGL(knn_select_kernel<KnnJaccardKey>, dim3((unsigned)m), dim3(kKnnBlock), 0, st, counts, n, deg,
                      qdeg, KnnJaccardKey{}, (int)k, P, out_w, out_n);
+  PS_CHECK_LAUNCH();
+  return kOk;
+}
+
+int launch_knn_select_score(const float* scores, int64_t n, int64_t m, int64_t k, float* out_w, int64_t* out_n,
+                            hipStream_t st) {
+  PS_REQUIRE(n > 0 && n <= INT32_MAX && m >= 0 && m <= 65535, kErrArg, "knn: bad sizes");
+  PS_REQUIRE(k >= 1 && k <= n && k <= kKnnMaxK, kErrArg, "knn: need 1 <= k <= min(n, 4096)");
+  if (m == 0) return kOk;
+  int P = 64;
+  while (P < k) P <<= 1;
+  // the policy reads neither the per-column array nor the row scalar, but the
+  // kernel's text loads both: the first score row (n floats, aligned as a row)
+  // and the first m <= m * n scores are valid memory for them
+  hipLaunchKernelGGL(knn_select_kernel<KnnScoreKey>, dim3((unsigned)m), dim3(kKnnBlock), 0, st, scores, n, scores,
+                     scores, KnnScoreKey{}, (int)k, P, out_w, out_n);
   PS_CHECK_LAUNCH();
   return kOk;
 }

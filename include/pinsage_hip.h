@@ -806,6 +806,39 @@ int pinsage_cooc_jaccard(const int64_t* t2c_ptr, const int32_t* t2c_idx, const i
                          int64_t nq, int64_t k, void* scratch, int64_t scratch_bytes, float* out_w, int64_t* out_n,
                          int* err, void* stream);
 
+/* The weighted form, behind the link-prediction indices of SimpleSimilarity
+ * (baselines.py:153-191; Adamic-Adar).  The two CSRs are read as node ->
+ * middle nodes and middle node -> nodes, in the layout above; for a graph's
+ * own adjacency (the projected track graph) both are that adjacency.
+ * wt int64 [n_cols] (device; null only where n_cols == 0) is a weight per
+ * middle node:
+ *   S(q, t) = sum of wt[c] over the middle nodes c adjacent to both q and t,
+ * in 64-bit integer adds (wrapping; independent of the order, so two runs give
+ * the same bits).  The track range is tiled through LDS in tiles of
+ * pinsage_cooc_weighted_tile() 64-bit counters; no global atomic, no memset,
+ * every output element is written exactly once.
+ *
+ * pinsage_cooc_weighted_sums: out int64 [nq][n_tracks], out[i][t] = S(queries[i], t).
+ *
+ * pinsage_cooc_weighted_knn: score(q, t) = float32(S(q, t)) * 2^-30 (the
+ * int64 -> float32 conversion rounds to nearest even; the weights are 2^30
+ * fixed point and the sums >= 0), out_w f32 [nq][k] / out_n int64 [nq][k]: the
+ * k largest per query in pinsage_cooc_jaccard's order, by the same selection
+ * kernel.  scratch: 16-byte aligned device bytes >=
+ * pinsage_cooc_weighted_scratch_bytes(n_tracks, rows) for some batch of
+ * rows >= 1 (the float score rows of one batch live there).
+ *
+ * Sizes, k, queries, err and refused calls as for pinsage_cooc_jaccard. */
+int64_t pinsage_cooc_weighted_tile(void);
+int64_t pinsage_cooc_weighted_scratch_bytes(int64_t n_tracks, int64_t batch_rows);
+int pinsage_cooc_weighted_sums(const int64_t* t2c_ptr, const int32_t* t2c_idx, const int64_t* c2t_ptr,
+                               const int32_t* c2t_idx, int64_t n_tracks, int64_t n_cols, const int64_t* wt,
+                               const int64_t* queries, int64_t nq, int64_t* out, int* err, void* stream);
+int pinsage_cooc_weighted_knn(const int64_t* t2c_ptr, const int32_t* t2c_idx, const int64_t* c2t_ptr,
+                              const int32_t* c2t_idx, int64_t n_tracks, int64_t n_cols, const int64_t* wt,
+                              const int64_t* queries, int64_t nq, int64_t k, void* scratch, int64_t scratch_bytes,
+                              float* out_w, int64_t* out_n, int* err, void* stream);
+
 /* ------------------------------------------------------------------ implicit-feedback ALS
  * The fit behind ColTrackCfALS / TrackTrackCfALS (baselines.py:458-514), which
  * the reference takes from implicit.cpu.als.AlternatingLeastSquares: the model
