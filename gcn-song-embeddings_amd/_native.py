@@ -207,6 +207,12 @@ _SIGS = {
     "pinsage_sgns_dense": (ctypes.c_int, [vp, i64, i64, vp, vp, i64, i64, i64, vp, i64, vp]),
     "pinsage_sgns_update": (ctypes.c_int, [vp, vp, vp, vp, i64, vp, i64, i64, vp, i64, i64, vp, i64, vp, i64, f32,
                                            f32, vp, vp]),
+    "pinsage_sage_neighbours": (ctypes.c_int, [vp, vp, vp, i64, vp, i64, i64, ctypes.c_uint64, i64, ctypes.c_uint32, vp,
+                                               vp, vp, vp]),
+    "pinsage_sage_negatives": (ctypes.c_int, [vp, vp, i64, vp, i64, i64, ctypes.c_uint64, i64, ctypes.c_uint32, vp, vp,
+                                              vp]),
+    "pinsage_sage_margin_loss": (ctypes.c_int, [vp, i64, i64, vp, i64, i64, i64, f32, vp, vp, vp, vp, vp, i64, vp]),
+    "pinsage_sage_lrelu_backward": (ctypes.c_int, [vp, i64, vp, i64, i64, i64, vp, i64, vp]),
     "pinsage_engine_create": (ctypes.c_int, [ctypes.POINTER(EngineConfig), ctypes.POINTER(vp)]),
     "pinsage_engine_destroy": (None, [vp]),
     "pinsage_engine_live_count": (i64, []),

@@ -53,8 +53,17 @@ preferential attachment from one sort of the degrees.  ``JaccardIndex`` computes
 the Jaccard coefficient, not the preferential attachment the reference assigns
 to that name.
 
-The reference's other baseline recommenders (lib/gnns)
-and implicit's own sampled-SGD order for bpr are out of scope; their libraries are not part of this
+``GraphSAGE`` (baselines.py:517-544, standing on lib/gnns) stands on ``SAGE``:
+unsupervised two-layer GraphSAGE with the MEAN aggregator, Floyd neighbour
+samples, walk positives and one-hop-excluded negatives on the Philox generator
+and the min / max cosine margin loss (csrc/sage.hip: a sampler, a negative
+draw and a loss kernel; the dense work on the GEMM, the segmented weighted mean
+and the Adam kernel).  The reference class cannot run as written, so this is
+again this package's own definition, deterministic, with no reference numbers;
+the quality of the defaults on real data is unmeasured.
+
+Implicit's own sampled-SGD order for bpr and the GAT / GCN variants of the
+reference's GNN library are out of scope; their libraries are not part of this
 build.  Names, signatures, return types and RNG consumption
 follow the reference; compute runs in HIP (no CPU fallback).
 """
@@ -1455,6 +1464,30 @@ def sgns_objective(C, U, V, negative, noise, regularization):
     return float(total - 0.5 * float(regularization) * ((U * U).sum() + (V * V).sum()))
 
 
+def _graph_arrays(graph_csr, who):
+    """(ptr, idx, weight or None, cum or None, n) of a graph tuple on the GPU,
+    checked to fit together: cum holds per row the inclusive prefix sum of the
+    weights (the walk kernel's form)."""
+    ptr, idx, weight, n = graph_csr
+    n = int(n)
+    ptr = torch.as_tensor(ptr).to(device="cuda", dtype=torch.int64).contiguous()
+    idx = torch.as_tensor(idx).to(device="cuda", dtype=torch.int32).contiguous()
+    if n < 1 or int(ptr.numel()) != n + 1 or int(ptr[0]) != 0 or int(ptr[-1]) != int(idx.numel()) \
+            or bool((ptr[1:] < ptr[:-1]).any()):
+        raise ValueError(f"{who}: the CSR arrays do not fit together")
+    if idx.numel() and (int(idx.min()) < 0 or int(idx.max()) >= n):
+        raise IndexError(f"{who}: neighbour ids out of range for {n} nodes")
+    wt = cum = None
+    if weight is not None:
+        wt = torch.as_tensor(weight).to(device="cuda", dtype=torch.int64).contiguous()
+        if int(wt.numel()) != int(idx.numel()) or (wt.numel() and int(wt.min()) < 1):
+            raise ValueError(f"{who}: weights must be positive integers, one per edge")
+        run = torch.cumsum(wt, 0)
+        before = torch.cat([torch.zeros(1, dtype=torch.int64, device="cuda"), run])[ptr[:-1]]
+        cum = (run - torch.repeat_interleave(before, ptr[1:] - ptr[:-1])).contiguous()
+    return ptr, idx, wt, cum, n
+
+
 N2V_MAX_BIAS_RATIO = 16.0  # the walk kernel's bound on max(1/p, 1, 1/q) / min(1/p, 1, 1/q)
 
 
@@ -1535,23 +1568,7 @@ class Node2Vec(_RowFit):
         self.embedding = self.context_factors = self.cooccurrence = self.noise = self.walks = None
 
     def _graph(self, graph_csr):
-        ptr, idx, weight, n = graph_csr
-        n = int(n)
-        ptr = torch.as_tensor(ptr).to(device="cuda", dtype=torch.int64).contiguous()
-        idx = torch.as_tensor(idx).to(device="cuda", dtype=torch.int32).contiguous()
-        if n < 1 or int(ptr.numel()) != n + 1 or int(ptr[0]) != 0 or int(ptr[-1]) != int(idx.numel()) \
-                or bool((ptr[1:] < ptr[:-1]).any()):
-            raise ValueError("Node2Vec: the CSR arrays do not fit together")
-        if idx.numel() and (int(idx.min()) < 0 or int(idx.max()) >= n):
-            raise IndexError(f"Node2Vec: neighbour ids out of range for {n} nodes")
-        cum = None
-        if weight is not None:
-            wt = torch.as_tensor(weight).to(device="cuda", dtype=torch.int64)
-            if int(wt.numel()) != int(idx.numel()) or (wt.numel() and int(wt.min()) < 1):
-                raise ValueError("Node2Vec: weights must be positive integers, one per edge")
-            run = torch.cumsum(wt, 0)
-            before = torch.cat([torch.zeros(1, dtype=torch.int64, device="cuda"), run])[ptr[:-1]]
-            cum = (run - torch.repeat_interleave(before, ptr[1:] - ptr[:-1])).contiguous()
+        ptr, idx, _, cum, n = _graph_arrays(graph_csr, "Node2Vec")
         return ptr, idx, cum, n
 
     def sample_walks(self, graph_csr, seed):
@@ -1639,6 +1656,389 @@ class FastNode2Vec(EmbeddingModel):
         self.model = Node2Vec(dim=128, walk_length=20, context=10, p=2.0, q=0.5, walks_per_node=10)
         self.model.fit(graph_csr)
         self.embedding = self.model.embedding[:len(ids)].cpu()
+
+    def embed(self, nodeset):
+        return self.embedding[torch.as_tensor(nodeset).cpu(), :]
+
+    def knn(self, nodeset, k):
+        return knn_from_emb(self.embedding, nodeset, k)
+
+
+# ----------------------------------------------------------------------------- GraphSAGE
+# baselines.py:517-544 on lib/gnns/GNNs_unsupervised.py.
+SAGE_MAX_FANOUT = 32     # kSageMaxFanout (csrc/sage.h)
+SAGE_MAX_POSITIVES = 64  # kSageMaxPos
+SAGE_MAX_NEGATIVES = 16  # kSageMaxNeg
+SAGE_MAX_DIM = 512       # kSageMaxD
+SAGE_BETAS, SAGE_EPS = (0.9, 0.999), 1e-8
+
+
+class SAGE:
+    """Unsupervised two-layer GraphSAGE with the MEAN aggregator (Hamilton, Ying,
+    Leskovec 2017) on the kernels of csrc/sage.hip, the GEMM, the segmented
+    weighted mean and the Adam kernel: what the reference's ``GraphSAGE`` builds
+    from lib/gnns/GNNs_unsupervised.py.  That class cannot run as written (it
+    reads ``self.proj_adj_mat`` and ``self.mode``, which do not exist), so there
+    are no reference numbers.  The model is THIS PROJECT'S DEFINITION,
+    deterministic and stated here in full (csrc/sage.h states it again, next to
+    the kernels); the quality of the defaults on real data is unmeasured.
+
+    Graph and features.  The graph is the tuple (ptr int64 [n + 1], idx int32,
+    weight int64 or None, n) of ``project_bipartite_graph``: an undirected CSR,
+    rows strictly ascending, no self loops, positive integer weights.  Features
+    X0 f32 [n, d_in].  Weights W1 [emb_size, 2 d_in], W2 [emb_size, 2 emb_size],
+    no bias, as the reference's SageLayer.
+
+    Neighbour sample (r, v), fanout S = ``num_sample``, deg the length of row v.
+    - deg <= S: positions 0 .. deg - 1 in CSR order; the other slots are void
+      (nb = -1, w = 0).
+    - Otherwise Floyd's algorithm, for j = 0 .. S - 1:
+
+        m = deg - S + j + 1
+        (r0, r1, r2, r3) = Philox4x32-10(key = seed, ctr = (r * 64 + j, v lo, v hi, offset))
+        t = ((r0 | r1 << 32) * m) >> 64
+        c_j = m - 1 if t is among c_0 .. c_{j-1}, else t
+
+    - Slot j holds nb = idx[row start + c_j]; its raw weight is
+      a_j = sqrtf((float)weight_e), 1 on an unweighted graph (the reference
+      mask's sqrt(edge count)); w_j = a_j / (a_0 + a_1 + ...), summed in slot
+      order from 0 in fp32, then one division (the reference's L1 normalisation).
+    - The sample depends on (seed, offset, r, v, row v) only.
+
+    Positives of step r with batch b_0 .. b_{B-1}: walk w < ``n_walks`` of anchor
+    i is pinsage_n2v_walk on the same graph with 1/p = 1/q = 1, length
+    ``walk_len`` + 1, offset 0 and position (r * batch_size + i) * n_walks + w.
+    Walk positions 1 .. walk_len are the P = n_walks * walk_len positive slots
+    in walk-major order; a slot is void if it is -1 or equals the anchor.
+
+    Negatives: Q = ``negatives`` slots per anchor a, sample s < Q, tries
+    k = 0 .. 15:  ctr = (r * 16 + k, (a Q + s) lo, hi, offset),
+    j = (uint64(r0) * n) >> 32, accept the first j != a that is not in row a
+    (binary search); void after 16 rejections.  The reference excludes the whole
+    5-hop ball, which on a projected track graph is nearly every node; ONE HOP
+    is used here.
+
+    Forward.  The group of anchor i is G = 1 + P + Q slots: the anchor, its
+    positives, its negatives.  T is the list of the B G slot nodes with repeats,
+    void slots as node 0 and flagged.  Layer 2 uses sample (2r + 1, t) for each t
+    in T; U is the sorted unique set of T and its neighbours; layer 1 uses
+    sample (2r, u) for each u in U.
+
+        H1[u] = lrelu(W1 [X0[u] || sum_j w_j X0[nb_j]])
+        Z[t]  = lrelu(W2 [H1[t] || sum_j w_j H1[nb_j]])
+
+    lrelu is the GEMM epilogue's leaky ReLU with slope 0.01; the reference uses
+    plain ReLU, a stated deviation.
+
+    Loss.  c(a, x) = z_a.z_x / max(sqrt(|z_a|^2 |z_x|^2), 1e-8); over the non-void
+    slots c_pos = the smallest positive cosine and c_neg = the largest negative
+    cosine, ties to the lowest slot (the reference's min / max of log sig(cos):
+    log sig is monotone);  loss_a = max(0, log sig(c_neg) - log sig(c_pos) +
+    margin).  An anchor is active with at least one non-void positive and one
+    non-void negative; the step's loss is the sum over active anchors divided by
+    max(1, #active).  Only the rows a, pos*, neg* of a group receive gradient.
+
+    Backward: dPre2 = dZ * lrelu'(Z);  dW2 = dPre2^T [H1[t] || Agg2] (the GEMM's
+    two-segment form);  [dSelf | dAgg] = dPre2 W2;  dH1[u] = the sum over the
+    slots and sample entries that read u, one pinsage_segment_wmean call with
+    normalize = 0 over the [2 B G, emb_size] view of [dSelf | dAgg] on a CSR
+    sorted by u with entries ordered by (t, self before neighbours, j);
+    dPre1 = dH1 * lrelu'(H1);  dW1 = dPre1^T [X0[u] || Agg1].  The features get
+    no gradient.  Update: one pinsage_adam per weight, torch's Adam with
+    ``learning_rate``, betas 0.9 / 0.999, eps 1e-8; the reference's SGD at
+    lr = 0.7 with gradient clipping is not reproduced.
+
+    Epochs.  Epoch e orders the nodes by torch.randperm(n,
+    generator=torch.Generator().manual_seed((seed + e) % 2**63)); steps are
+    consecutive slices of ``batch_size`` (the reference's 20 wastes the GPU: 64);
+    the step counter r runs across epochs.  ``embeddings`` runs both layers over
+    all n nodes with rounds 2 R and 2 R + 1, R the number of steps of the fit,
+    which the fit never uses.
+
+    Randomness.  The seed is ``random_state`` or, with None, one
+    ``torch.randint(0, 2**63 - 1, (1,))`` from torch's global generator; then
+    ``xavier_uniform_`` for W1, then for W2, on the CPU from the global
+    generator.
+
+    Between the kernels the index arrays (unique, local ids, the transposed
+    CSR) are plain torch; the step loop reads no device value on the host.
+    ``gemm_prec`` (-1: the library's default, split bf16 with fp32-level error;
+    0: fp32 MFMA) is the product arithmetic of the two forward GEMMs."""
+
+    def __init__(self, emb_size=128, num_sample=10, n_walks=4, walk_len=4, negatives=6, margin=3.0, epochs=5,
+                 batch_size=64, learning_rate=1e-3, random_state=None):
+        inf = float("inf")
+        if not (emb_size == int(emb_size) and 4 <= int(emb_size) <= SAGE_MAX_DIM and int(emb_size) % 4 == 0):
+            raise ValueError(f"SAGE: emb_size = {emb_size}: need a multiple of 4 in [4, {SAGE_MAX_DIM}]")
+        if not (num_sample == int(num_sample) and 1 <= int(num_sample) <= SAGE_MAX_FANOUT):
+            raise ValueError(f"SAGE: num_sample = {num_sample}: need an integer in [1, {SAGE_MAX_FANOUT}]")
+        if not (n_walks == int(n_walks) and walk_len == int(walk_len) and int(n_walks) >= 1 and int(walk_len) >= 1
+                and int(n_walks) * int(walk_len) <= SAGE_MAX_POSITIVES):
+            raise ValueError(f"SAGE: need n_walks, walk_len >= 1 and n_walks * walk_len <= {SAGE_MAX_POSITIVES}")
+        if not (negatives == int(negatives) and 1 <= int(negatives) <= SAGE_MAX_NEGATIVES):
+            raise ValueError(f"SAGE: negatives = {negatives}: need an integer in [1, {SAGE_MAX_NEGATIVES}]")
+        if not (-inf < margin < inf and 0 <= learning_rate < inf and int(epochs) >= 0 and int(batch_size) >= 1):
+            raise ValueError("SAGE: need a finite margin, finite learning_rate >= 0, epochs >= 0, batch_size >= 1")
+        self.emb_size, self.num_sample = int(emb_size), int(num_sample)
+        self.n_walks, self.walk_len, self.negatives = int(n_walks), int(walk_len), int(negatives)
+        self.margin, self.epochs, self.batch_size = float(margin), int(epochs), int(batch_size)
+        self.learning_rate, self.random_state = float(learning_rate), random_state
+        self.gemm_prec = -1
+        self.weights = self.losses = None
+        self.steps = 0
+
+    # ------------------------------------------------------------------ intake
+    def prepare(self, graph, features, weights=None):
+        """Takes the graph and the features to the GPU, checks them, draws the
+        seed and the initial weights (given ``weights`` = (W1, W2) are copied
+        after the draws) and resets the optimiser.  ``fit`` starts with it."""
+        nat.require_gpu()
+        ptr, idx, wt, cum, n = _graph_arrays(graph, "SAGE")
+        rows = _csr_rows(ptr)
+        if bool(((idx[1:] <= idx[:-1]) & (rows[1:] == rows[:-1])).any()):
+            raise ValueError("SAGE: rows must be strictly ascending (the negative draw binary-searches the row)")
+        X0 = torch.as_tensor(features)
+        if X0.dim() != 2 or int(X0.shape[0]) != n:
+            raise ValueError(f"SAGE: features of shape {tuple(X0.shape)}, expected [{n}, d_in]")
+        d_in = int(X0.shape[1])
+        if d_in < 4 or d_in % 4:
+            raise ValueError(f"SAGE: d_in = {d_in}: the GEMM needs a multiple of 4")
+        self._graph = (ptr, idx, wt, cum, n)
+        self._X0 = X0.to(device="cuda", dtype=torch.float32).contiguous()
+        if self.random_state is None:
+            self._seed = int(torch.randint(0, 2 ** 63 - 1, (1,)))
+        else:
+            self._seed = int(self.random_state) & (2 ** 64 - 1)
+        out = self.emb_size
+        W = [torch.nn.init.xavier_uniform_(torch.empty(out, 2 * d_in)),
+             torch.nn.init.xavier_uniform_(torch.empty(out, 2 * out))]
+        if weights is not None:
+            for k, given in enumerate(weights):
+                g = torch.as_tensor(given)
+                if tuple(g.shape) != tuple(W[k].shape):
+                    raise ValueError(f"SAGE: W{k + 1} of shape {tuple(g.shape)}, expected {tuple(W[k].shape)}")
+                W[k] = g
+        self.weights = [w.to(device="cuda", dtype=torch.float32, copy=True).contiguous() for w in W]
+        self._m = [torch.zeros_like(w) for w in self.weights]
+        self._v = [torch.zeros_like(w) for w in self.weights]
+        self._err = torch.zeros(1, dtype=torch.int32, device="cuda")
+        self.steps, self.losses = 0, []
+        return self
+
+    # ------------------------------------------------------------------ launches
+    def _gemm(self, what, **kw):
+        import ctypes
+        p = nat.GemmParams(**kw)
+        rc = nat.lib().pinsage_gemm_params(ctypes.byref(p), None, nat.stream_ptr())
+        if rc == -2:
+            raise ValueError(f"SAGE: {what}: " + nat.lib().pinsage_last_error().decode(errors="replace"))
+        nat.check(rc, what)
+
+    def sample(self, nodes, round):
+        """(nb int32 [m, num_sample], w float32 [m, num_sample]) on the GPU: the
+        neighbour sample (round, v) of every v in ``nodes`` (pinsage_sage_neighbours)."""
+        ptr, idx, wt, _, n = self._graph
+        nodes = torch.as_tensor(nodes).to(device="cuda", dtype=torch.int64).contiguous()
+        m, S = int(nodes.numel()), self.num_sample
+        nb = torch.empty((m, S), dtype=torch.int32, device="cuda")
+        w = torch.empty((m, S), dtype=torch.float32, device="cuda")
+        nat.check(nat.lib().pinsage_sage_neighbours(nat.ptr(ptr), nat.ptr(idx), nat.ptr(wt), n, nat.ptr(nodes), m, S,
+                                                    self._seed, int(round), 0, nat.ptr(nb), nat.ptr(w),
+                                                    nat.ptr(self._err), nat.stream_ptr()), "sage_neighbours")
+        return nb, w
+
+    def _slots(self, batch, r):
+        """int32 [B, G]: the anchor, its positives and its negatives, -1 = void."""
+        ptr, idx, _, cum, n = self._graph
+        B, L = int(batch.numel()), self.walk_len + 1
+        starts = batch.repeat_interleave(self.n_walks).contiguous()
+        walks = torch.empty((B * self.n_walks, L), dtype=torch.int32, device="cuda")
+        nat.check(nat.lib().pinsage_n2v_walk(nat.ptr(ptr), nat.ptr(idx), nat.ptr(cum), n, nat.ptr(starts),
+                                             int(starts.numel()), L, 1.0, 1.0, self._seed, 0,
+                                             int(r) * self.batch_size * self.n_walks, nat.ptr(walks),
+                                             nat.ptr(self._err), nat.stream_ptr()), "n2v_walk")
+        anchor = batch.to(torch.int32)[:, None]
+        pos = walks[:, 1:].reshape(B, self.n_walks * self.walk_len)
+        pos = torch.where(pos == anchor, torch.full_like(pos, -1), pos)
+        neg = torch.empty((B, self.negatives), dtype=torch.int32, device="cuda")
+        nat.check(nat.lib().pinsage_sage_negatives(nat.ptr(ptr), nat.ptr(idx), n, nat.ptr(batch), B, self.negatives,
+                                                   self._seed, int(r), 0, nat.ptr(neg), nat.ptr(self._err),
+                                                   nat.stream_ptr()), "sage_negatives")
+        return torch.cat([anchor, pos, neg], 1).contiguous()
+
+    def _layer(self, h, self_idx, cols, w, W, rows_alloc):
+        """lrelu(W [h[self_idx] || sum_j w_j h[cols_j]]) for the len(self_idx) rows:
+        (the aggregate, the output), the aggregate with rows_alloc >= rows rows,
+        the tail zero (the weight gradient's K is a multiple of 4)."""
+        m, S, d, out = int(self_idx.numel()), self.num_sample, int(h.shape[1]), self.emb_size
+        agg = torch.empty((rows_alloc, d), dtype=torch.float32, device="cuda")
+        if rows_alloc > m:
+            agg[m:].zero_()
+        seg = torch.arange(0, (m + 1) * S, S, dtype=torch.int64, device="cuda")
+        nat.check(nat.lib().pinsage_segment_wmean(nat.ptr(h), h.stride(0), int(h.shape[0]), d, nat.ptr(seg),
+                                                  nat.ptr(cols), nat.ptr(w), m, 0, nat.ptr(agg), agg.stride(0),
+                                                  nat.stream_ptr()), "segment_wmean")
+        y = torch.empty((m, out), dtype=torch.float32, device="cuda")
+        self._gemm("layer", M=m, N=out, K=2 * d, a=h.data_ptr(), lda=h.stride(0), a_idx=self_idx.data_ptr(), K1=d,
+                   a2=agg.data_ptr(), lda2=agg.stride(0), b=W.data_ptr(), ldb=W.stride(0), c=y.data_ptr(),
+                   ldc=y.stride(0), act=1, prec=self.gemm_prec)
+        return agg, y
+
+    def _dpre(self, y, dy, rows_alloc):
+        """dy * lrelu'(y) with rows_alloc >= rows rows, the tail zero."""
+        m, out = int(y.shape[0]), int(y.shape[1])
+        dp = torch.empty((rows_alloc, out), dtype=torch.float32, device="cuda")
+        if rows_alloc > m:
+            dp[m:].zero_()
+        nat.check(nat.lib().pinsage_sage_lrelu_backward(nat.ptr(y), y.stride(0), nat.ptr(dy), dy.stride(0), m, out,
+                                                        nat.ptr(dp), dp.stride(0), nat.stream_ptr()),
+                  "sage_lrelu_backward")
+        return dp
+
+    def _wgrad(self, dp, h, self_idx, agg):
+        """dp^T [h[self_idx] || agg]: [emb_size, d + d], K = the rows of dp."""
+        K, out, d = int(dp.shape[0]), int(dp.shape[1]), int(h.shape[1])
+        dW = torch.empty((out, 2 * d), dtype=torch.float32, device="cuda")
+        self._gemm("weight gradient", M=out, N=2 * d, K=K, a_kmajor=0, b_kmajor=0, a=dp.data_ptr(), lda=dp.stride(0),
+                   b=h.data_ptr(), ldb=h.stride(0), b_idx=self_idx.data_ptr(), N1=d, b2=agg.data_ptr(),
+                   ldb2=agg.stride(0), c=dW.data_ptr(), ldc=dW.stride(0))
+        return dW
+
+    @staticmethod
+    def _pad4(idx32):
+        """idx32 with zeros appended up to a multiple of 4 entries."""
+        extra = -int(idx32.numel()) % 4
+        return torch.cat([idx32, idx32.new_zeros(extra)]).contiguous() if extra else idx32
+
+    def step_tensors(self, batch, r):
+        """One step r on ``batch`` (node ids) from the current weights, without
+        updating: a dict of slots [B, G], T, U, the sample tables (nb1, w1) of U
+        and (nb2, w2) of T, H1, Z, the per-anchor loss, active and sel, dZ, the
+        step's loss (a device scalar) and the gradients dW1, dW2."""
+        L = nat.lib()
+        _, _, _, _, n = self._graph
+        X0, (W1, W2) = self._X0, self.weights
+        out, S = self.emb_size, self.num_sample
+        P, Q = self.n_walks * self.walk_len, self.negatives
+        batch = torch.as_tensor(batch).to(device="cuda", dtype=torch.int64).contiguous()
+        B, G = int(batch.numel()), 1 + P + Q
+        slots = self._slots(batch, r)
+        T = slots.clamp(min=0).reshape(-1).to(torch.int64)
+        nb2, w2 = self.sample(T, 2 * r + 1)
+        U = torch.unique(torch.cat([T, nb2[nb2 >= 0].to(torch.int64)]))
+        nb1, w1 = self.sample(U, 2 * r)
+        nU, nT = int(U.numel()), B * G
+        nUp, nTp = nU + (-nU) % 4, nT + (-nT) % 4
+        U32 = self._pad4(U.to(torch.int32))
+        t_loc = self._pad4(torch.searchsorted(U, T).to(torch.int32))
+        nb2_loc = torch.where(nb2 >= 0, torch.searchsorted(U, nb2.clamp(min=0).to(torch.int64)).to(torch.int32), nb2)
+        nb2_loc = nb2_loc.contiguous()
+        # forward
+        agg1, H1 = self._layer(X0, U32[:nU], nb1, w1, W1, nUp)
+        agg2, Z = self._layer(H1, t_loc[:nT], nb2_loc, w2, W2, nTp)
+        # loss
+        void = slots < 0
+        act = (~void[:, 1:1 + P]).any(1) & (~void[:, 1 + P:]).any(1) & ~void[:, 0]
+        scale = (1.0 / act.sum().clamp(min=1).to(torch.float32)).reshape(1)
+        loss_a = torch.empty(B, dtype=torch.float32, device="cuda")
+        active = torch.empty(B, dtype=torch.int32, device="cuda")
+        sel = torch.empty((B, 2), dtype=torch.int32, device="cuda")
+        dZ = torch.empty((nT, out), dtype=torch.float32, device="cuda")
+        nat.check(L.pinsage_sage_margin_loss(nat.ptr(Z), Z.stride(0), out, nat.ptr(slots), B, P, Q, self.margin,
+                                             nat.ptr(scale), nat.ptr(loss_a), nat.ptr(active), nat.ptr(sel),
+                                             nat.ptr(dZ), dZ.stride(0), nat.stream_ptr()), "sage_margin_loss")
+        # backward
+        dP2 = self._dpre(Z, dZ, nTp)
+        dW2 = self._wgrad(dP2, H1, t_loc, agg2)
+        dSA = torch.empty((nT, 2 * out), dtype=torch.float32, device="cuda")
+        self._gemm("input gradient", M=nT, N=2 * out, K=out, b_kmajor=0, a=dP2.data_ptr(), lda=dP2.stride(0),
+                   b=W2.data_ptr(), ldb=W2.stride(0), c=dSA.data_ptr(), ldc=dSA.stride(0))
+        # the transposed CSR over U: per t its own row of dSelf, then its sample's rows of dAgg
+        t = torch.arange(nT, dtype=torch.int32, device="cuda")[:, None]
+        key = torch.cat([t_loc[:nT, None], nb2_loc], 1).reshape(-1)
+        col = torch.cat([2 * t, (2 * t + 1).expand(nT, S)], 1).reshape(-1)
+        wt = torch.cat([torch.ones((nT, 1), dtype=torch.float32, device="cuda"), w2], 1).reshape(-1)
+        ok = key >= 0
+        key = key[ok].to(torch.int64)
+        order = torch.sort(key, stable=True).indices
+        colT, wT, ptrT = col[ok][order].contiguous(), wt[ok][order].contiguous(), _csr_ptr(key, nU)
+        dH1 = torch.empty((nU, out), dtype=torch.float32, device="cuda")
+        nat.check(L.pinsage_segment_wmean(dSA.data_ptr(), out, 2 * nT, out, nat.ptr(ptrT), nat.ptr(colT), nat.ptr(wT),
+                                          nU, 0, nat.ptr(dH1), dH1.stride(0), nat.stream_ptr()), "segment_wmean")
+        dP1 = self._dpre(H1, dH1, nUp)
+        dW1 = self._wgrad(dP1, X0, U32, agg1)
+        return dict(slots=slots, T=T, U=U, nb1=nb1, w1=w1, nb2=nb2, w2=w2, H1=H1, Z=Z, loss_a=loss_a, active=active,
+                    sel=sel, dZ=dZ, loss=loss_a.sum() * scale[0], dW1=dW1, dW2=dW2)
+
+    def _adam(self, grads):
+        self.steps += 1
+        b1, b2 = SAGE_BETAS
+        coef = torch.tensor([self.learning_rate / (1.0 - b1 ** self.steps), (1.0 - b2 ** self.steps) ** 0.5],
+                            dtype=torch.float32).to("cuda")
+        for p, g, m, v in zip(self.weights, grads, self._m, self._v):
+            nat.check(nat.lib().pinsage_adam(nat.ptr(p), nat.ptr(g), nat.ptr(m), nat.ptr(v), int(p.numel()),
+                                             nat.ptr(coef), b1, b2, SAGE_EPS, nat.stream_ptr()), "adam")
+
+    def fit(self, graph, features, callback=None, weights=None):
+        """graph: (ptr, idx, weight or None, n); features [n, d_in].  Rows not
+        strictly ascending or arrays that do not fit together raise ValueError,
+        neighbour ids out of range IndexError, shapes the GEMM refuses
+        ValueError.  ``callback(step, self)`` runs after every step
+        (monitoring).  Sets ``weights`` and ``losses`` (one float per step, read
+        back once at the end)."""
+        self.prepare(graph, features, weights)
+        n = self._graph[4]
+        per_epoch = -(-n // self.batch_size)
+        if 2 * self.epochs * per_epoch + 2 > 1 << 25:
+            raise ValueError("SAGE: sample round 2 * steps + 1 must stay below 2^25")
+        losses, r = [], 0
+        for e in range(self.epochs):
+            order = torch.randperm(n, generator=torch.Generator().manual_seed((self._seed + e) % 2 ** 63)).to("cuda")
+            for b0 in range(0, n, self.batch_size):
+                st = self.step_tensors(order[b0:b0 + self.batch_size], r)
+                self._adam((st["dW1"], st["dW2"]))
+                losses.append(st["loss"])
+                r += 1
+                if callback is not None:
+                    callback(r - 1, self)
+        self._rounds = r
+        self.losses = torch.stack(losses).cpu().tolist() if losses else []
+        if int(self._err):
+            raise IndexError(f"SAGE: node ids out of range for {n} nodes")
+        return self
+
+    def embeddings(self):
+        """float32 [n, emb_size] on the GPU: both layers over all n nodes with the
+        sample rounds 2 R and 2 R + 1, R the number of steps of the fit."""
+        n, R = self._graph[4], getattr(self, "_rounds", 0)
+        if 2 * R + 1 >= 1 << 25:
+            raise ValueError("SAGE: sample round 2 * steps + 1 must stay below 2^25")
+        nodes = torch.arange(n, dtype=torch.int64, device="cuda")
+        loc = nodes.to(torch.int32)
+        nb1, w1 = self.sample(nodes, 2 * R)
+        _, H1 = self._layer(self._X0, loc, nb1, w1, self.weights[0], n)
+        nb2, w2 = self.sample(nodes, 2 * R + 1)
+        return self._layer(H1, loc, nb2, w2, self.weights[1], n)[1]
+
+
+class GraphSAGE(EmbeddingModel):
+    """GraphSAGE embeddings of the tracks (baselines.py:517-544): ``SAGE`` with
+    its defaults on the weighted track-track projection and ``features``.
+    ``projected=False`` raises NotImplementedError: the bipartite graph's
+    collections have no features (the reference's line for it cannot run
+    either).  ``embedding`` is a CPU tensor as FastNode2Vec's."""
+
+    def __init__(self, projected=True):
+        self.model = None
+        self.embedding = None
+        self.projected = projected
+
+    def train(self, g, ids, train_set, test_set, features):
+        if not self.projected:
+            raise NotImplementedError("GraphSAGE: projected=False needs features of the collections; there are none")
+        self.model = SAGE()
+        self.model.fit(project_bipartite_graph(g, ids), torch.as_tensor(features)[:len(ids)])
+        self.embedding = self.model.embeddings().cpu()
 
     def embed(self, nodeset):
         return self.embedding[torch.as_tensor(nodeset).cpu(), :]

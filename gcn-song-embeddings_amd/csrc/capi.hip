@@ -13,6 +13,7 @@
 #include "bpr.h"
 #include "lmf.h"
 #include "n2v.h"
+#include "sage.h"
 #include "capi.h"
 #include "conv.h"
 #include "cooc.h"
@@ -835,6 +836,31 @@ int pinsage_n2v_walk(const int64_t* ptr, const int32_t* idx, const int64_t* cum,
                      uint32_t offset, int64_t walk_base, int32_t* walks, int* err, void* stream) {
   return launch_n2v_walk(ptr, idx, cum, n_nodes, starts, n_walks, length, inv_p, inv_q, seed, offset, walk_base, walks,
                          err, (hipStream_t)stream);
+}
+
+int pinsage_sage_neighbours(const int64_t* ptr, const int32_t* idx, const int64_t* weight, int64_t n_nodes,
+                            const int64_t* nodes, int64_t m, int64_t fanout, uint64_t seed, int64_t round,
+                            uint32_t offset, int32_t* nb, float* w, int* err, void* stream) {
+  return launch_sage_neighbours(ptr, idx, weight, n_nodes, nodes, m, fanout, seed, round, offset, nb, w, err,
+                                (hipStream_t)stream);
+}
+
+int pinsage_sage_negatives(const int64_t* ptr, const int32_t* idx, int64_t n_nodes, const int64_t* anchors, int64_t B,
+                           int64_t Q, uint64_t seed, int64_t round, uint32_t offset, int32_t* neg, int* err,
+                           void* stream) {
+  return launch_sage_negatives(ptr, idx, n_nodes, anchors, B, Q, seed, round, offset, neg, err, (hipStream_t)stream);
+}
+
+int pinsage_sage_margin_loss(const float* Z, int64_t ldz, int64_t d, const int32_t* slots, int64_t B, int64_t P,
+                             int64_t Q, float margin, const float* scale, float* loss, int32_t* active, int32_t* sel,
+                             float* dZ, int64_t lddz, void* stream) {
+  return launch_sage_margin_loss(Z, ldz, d, slots, B, P, Q, margin, scale, loss, active, sel, dZ, lddz,
+                                 (hipStream_t)stream);
+}
+
+int pinsage_sage_lrelu_backward(const float* y, int64_t ldy, const float* dy, int64_t lddy, int64_t n, int64_t d,
+                                float* dp, int64_t ldp, void* stream) {
+  return launch_sage_lrelu_backward(y, ldy, dy, lddy, n, d, dp, ldp, (hipStream_t)stream);
 }
 
 int pinsage_sgns_dense(const float* X, int64_t n_rows, int64_t ldx, const float* Y, const float* cw, int64_t n_other,

@@ -42,6 +42,9 @@ __device__ __forceinline__ float lmf_sigmoid(float s) {
   return (s >= 0.f ? 1.f : e) / (1.f + e);
 }
 
+// log(1 + exp(s)) with the same e: -lmf_softplus(-s) is log(lmf_sigmoid(s))
+__device__ __forceinline__ float lmf_softplus(float s) { return fmaxf(s, 0.f) + log1pf(expf(-fabsf(s))); }
+
 // WEIGHT form: by is the column weight cw; bx and dsum are unused (null)
 struct SigDenseArgs {
   const float* X;

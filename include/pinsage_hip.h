@@ -442,10 +442,11 @@ int pinsage_norm_lrelu_backward(const float* y, const float* norms, const float*
                                 float* dp, void* stream);
 
 /* ------------------------------------------------------------------ test entries
- * Nothing in the engine or the Python package's product path calls these: they
- * expose the engine's own launches, one at a time, to the tests
- * (tests/test_gpu_gemm_forms.py, tests/test_gpu_optimizer.py,
- * tests/test_gpu_sampler_edges.py).
+ * Nothing in the engine calls these: they expose the engine's own launches,
+ * one at a time, to the tests (tests/test_gpu_gemm_forms.py,
+ * tests/test_gpu_optimizer.py, tests/test_gpu_sampler_edges.py).  The GraphSAGE
+ * baseline (baselines.SAGE) runs its dense products and its Adam steps on
+ * pinsage_gemm_params and pinsage_adam.
  *
  * pinsage_gemm_params: one GEMM launch with every field of the library's
  * launch parameters (csrc/gemm.h GemmParams, which documents them) given by
@@ -1093,6 +1094,75 @@ int pinsage_bpr_sample(const int64_t* ptr, const int32_t* idx, int64_t n_rows, i
 int pinsage_bpr_apply(const int64_t* ptr, const int32_t* idx, const float* val, int64_t n_rows, const float* Y,
                       int64_t n_other, int64_t ldy, float* X, float* bx, int64_t ldx, int64_t f, float* H, int64_t ldh,
                       float* hb, float reg, float lr, int* err, void* stream);
+
+/* ------------------------------------------------------------------ unsupervised GraphSAGE
+ * Hamilton, Ying, Leskovec, "Inductive Representation Learning on Large Graphs"
+ * (2017), as this project defines it (csrc/sage.h states the whole model; the
+ * reference's GraphSAGE class, baselines.py:517-544, cannot run as written).
+ * The graph is an undirected CSR (ptr int64 [n_nodes + 1], idx int32 ascending
+ * per row, no duplicates, no self loops) with positive integer weights weight
+ * int64 [nnz] (null: unweighted).  All pointers are device memory.
+ *
+ * pinsage_sage_neighbours: nb int32 [m][fanout], w f32 [m][fanout], row i the
+ * neighbour sample (round, nodes[i]).  With deg the length of the node's row v:
+ *   deg <= fanout: positions 0 .. deg - 1 in CSR order, the other slots void
+ *     (nb = -1, w = 0);
+ *   otherwise Floyd's algorithm, for j = 0 .. fanout - 1:
+ *     m_j = deg - fanout + j + 1
+ *     (r0, r1, r2, r3) = Philox4x32-10(key = seed, ctr = (round * 64 + j, v lo, v hi, offset))
+ *     t = ((r0 | r1 << 32) * m_j) >> 64;  c_j = m_j - 1 if t is among c_0 .. c_{j-1}, else t
+ *   slot j: nb = idx[row start + c_j], a_j = sqrtf((float)weight) (1 unweighted),
+ *   w_j = a_j / (a_0 + a_1 + ...), the sum in slot order from 0 in fp32.
+ * The row depends on (seed, offset, round, v, row v) only.  One 32-lane half of
+ * a wave per node.  A node id outside [0, n_nodes), or a neighbour id in idx
+ * outside it, sets *err (nullable) and is clamped to 0.  Refused
+ * (PINSAGE_ERR_ARG, nothing launched, outputs untouched): fanout outside
+ * [1, 32]; round outside [0, 2^25); n_nodes outside [1, INT32_MAX]; m < 0 or
+ * above INT32_MAX; a null ptr or idx; null nodes, nb or w unless m == 0.
+ *
+ * pinsage_sage_negatives: neg int32 [B][Q], row i the negatives of anchors[i]
+ * = a.  Sample s < Q, tries k = 0 .. 15:
+ *   ctr = (round * 16 + k, (a Q + s) lo, hi, offset);  j = (uint64(r0) * n_nodes) >> 32
+ *   accept the first j != a that is not in row a (binary search); -1 after 16
+ *   rejections.
+ * One lane per sample.  An anchor outside [0, n_nodes) sets *err and is clamped
+ * to 0.  Refused: Q outside [1, 16]; round outside [0, 2^27); sizes and null
+ * pointers as above (B == 0 launches nothing).
+ *
+ * pinsage_sage_margin_loss: Z f32 [B G][ldz], G = 1 + P + Q, row a G + g the
+ * embedding of slot g of anchor group a (slot 0 the anchor, then P positives,
+ * then Q negatives); slots int32 [B][G], negative = void.  With
+ *   c(a, x) = z_a . z_x / max(sqrt(|z_a|^2 |z_x|^2), 1e-8)
+ * c_pos = the smallest cosine over the non-void positives, c_neg = the largest
+ * over the non-void negatives (ties: the lowest slot),
+ *   loss[a] = max(0, log sig(c_neg) - log sig(c_pos) + margin)
+ * for an active anchor (a non-void positive and a non-void negative), else 0;
+ * active[a] = 0 / 1; sel int32 [B][2] = the chosen positive and negative slot
+ * (index in the group) or -1; dZ f32 [B G][lddz] = *scale (device) times
+ * d loss[a] / d Z, every row written (zeros where nothing flows: only the rows
+ * a, pos*, neg* of a group can be non-zero).  One wave per group; a lane holds
+ * columns 2 lane + 128 c and the next, dots and squared norms are wave sums.
+ * sig and softplus as for logistic MF above.  A zero row gives cosine 0 through
+ * the clamp, never NaN.  Refused: d outside [4, 512] or d % 4 != 0; ldz or lddz
+ * below d or not a multiple of 4; Z or dZ not 16-byte aligned; P outside
+ * [1, 64]; Q outside [1, 16]; margin not finite; B < 0; a null pointer unless
+ * B == 0.
+ *
+ * pinsage_sage_lrelu_backward: dp[i][c] = dy[i][c] * (y[i][c] > 0 ? 1 : 0.01)
+ * for i < n, c < d: the backward of the GEMM epilogue's leaky ReLU from its
+ * output y (dp may be dy).  d % 4 == 0, leading dimensions >= d and multiples
+ * of 4, 16-byte aligned pointers. */
+int pinsage_sage_neighbours(const int64_t* ptr, const int32_t* idx, const int64_t* weight, int64_t n_nodes,
+                            const int64_t* nodes, int64_t m, int64_t fanout, uint64_t seed, int64_t round,
+                            uint32_t offset, int32_t* nb, float* w, int* err, void* stream);
+int pinsage_sage_negatives(const int64_t* ptr, const int32_t* idx, int64_t n_nodes, const int64_t* anchors, int64_t B,
+                           int64_t Q, uint64_t seed, int64_t round, uint32_t offset, int32_t* neg, int* err,
+                           void* stream);
+int pinsage_sage_margin_loss(const float* Z, int64_t ldz, int64_t d, const int32_t* slots, int64_t B, int64_t P,
+                             int64_t Q, float margin, const float* scale, float* loss, int32_t* active, int32_t* sel,
+                             float* dZ, int64_t lddz, void* stream);
+int pinsage_sage_lrelu_backward(const float* y, int64_t ldy, const float* dy, int64_t lddy, int64_t n, int64_t d,
+                                float* dp, int64_t ldp, void* stream);
 
 /* ------------------------------------------------------------------ train-step engine
  * PinSageModel.forward / PinSage.train_batch (pinsage_model.py:246-265,
