@@ -335,6 +335,101 @@ int pinsage_ppr_topk(const int64_t* indptr, const int32_t* indices, int64_t n_al
   return kOk;
 }
 
+// Early stop.  Workspace: [MT chunk states | err | words consumed | n_runs[R] | hops[R] |
+// runs[R][n_hops] | MT raw words[R][3 n_hops]] for R sources per round.
+static int64_t ppr_stop_round_bytes(int64_t n_hops, bool mt) { return 4 + ppr_round_bytes(n_hops, mt); }
+
+int64_t pinsage_ppr_topk_early_stop_workspace(int64_t n_src, int64_t n_hops, int rng_mt) {
+  return ppr_fixed_bytes() + 5 * 256 + std::max<int64_t>(n_src, 1) * ppr_stop_round_bytes(n_hops, rng_mt != 0);
+}
+
+int pinsage_ppr_topk_early_stop(const int64_t* indptr, const int32_t* indices, int64_t n_all, int64_t n_items,
+                                const int64_t* sources, int64_t n_src, int64_t n_hops, float alpha, int64_t k,
+                                int64_t stop_np, int64_t stop_nv, void* mt, uint64_t seed, uint32_t offset,
+                                int64_t src_base, void* ws, int64_t ws_bytes, double* w_out, int64_t* nb_out,
+                                float* wn_out, int32_t* nb32_out, int64_t t_norm, int32_t* hops_out,
+                                int64_t* words_out, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  PS_REQUIRE(n_src >= 0 && n_hops > 0 && n_all > 0 && n_items > 0, kErrArg, "ppr_topk_early_stop: bad sizes");
+  PS_REQUIRE(k >= 1 && k <= n_items, kErrArg,
+             "ppr_topk_early_stop: k out of range (torch: selected index k out of range)");
+  PS_REQUIRE(k * 64 <= n_items, kErrArg,
+             "ppr_topk_early_stop: the nth_element regime (k * 64 > n_items) is not implemented");
+  PS_REQUIRE(k + n_hops < 65536, kErrArg, "ppr_topk_early_stop: k too large");
+  PS_REQUIRE(n_hops <= kStopMaxHops, kErrArg, "ppr_topk_early_stop: n_hops too large for the LDS tables (2048)");
+  PS_REQUIRE(n_all < (int64_t)0xFFFFFFFF && n_items < (int64_t)0xFFFFFFFF, kErrArg,
+             "ppr_topk_early_stop: n_all and n_items must fit 32 bits");
+  PS_REQUIRE(!w_out == !nb_out && !wn_out == !nb32_out, kErrArg,
+             "ppr_topk_early_stop: an output pair is weights and ids");
+  PS_REQUIRE(!wn_out || (t_norm >= 1 && t_norm <= k), kErrArg, "ppr_topk_early_stop: t_norm must be in [1, k]");
+  if (words_out) *words_out = 0;
+  if (n_src == 0) return kOk;
+  // a count is at least 1 and at most n_hops: anything else never stops
+  const int np = (int)std::min<int64_t>(std::max<int64_t>(stop_np, 0), n_hops + 1);
+  const int nv = (int)std::min<int64_t>(std::max<int64_t>(stop_nv, 0), n_hops + 1);
+  const bool use_mt = mt != nullptr;
+  char* base = static_cast<char*>(ws);
+  MTChunk* desc_dev = reinterpret_cast<MTChunk*>(base);
+  const int64_t fixed = ppr_fixed_bytes();
+  int* err_dev = reinterpret_cast<int*>(base + fixed - 256);
+  int64_t* words_dev = reinterpret_cast<int64_t*>(base + fixed);
+  const int64_t room = (ws_bytes - fixed - 5 * 256) / ppr_stop_round_bytes(n_hops, use_mt);
+  PS_REQUIRE(ws && room >= 1, kErrWorkspace, "ppr_topk_early_stop: workspace too small for one source");
+  const int64_t R = std::min(room, n_src);
+  char* p = base + fixed + 256;
+  int* nr_dev = reinterpret_cast<int*>(p);
+  p += align_up(R * 4, 256);
+  int* hops_dev = reinterpret_cast<int*>(p);
+  p += align_up(R * 4, 256);
+  uint2* runs_dev = reinterpret_cast<uint2*>(p);
+  p += align_up(R * n_hops * 8, 256);
+  uint32_t* raw = reinterpret_cast<uint32_t*>(p);
+  PS_CHECK_HIP(hipMemsetAsync(err_dev, 0x7f, 4, st));
+  std::vector<MTChunk> desc(use_mt ? (size_t)kPprChunks : 0);
+  const int64_t per_src = 3 * n_hops;
+  int64_t words_total = 0;
+  for (int64_t r0 = 0; r0 < n_src; r0 += R) {
+    const int64_t nr = std::min(R, n_src - r0);
+    MTState at_round;  // the stream where this round's sources start
+    if (use_mt) {
+      MTState& g = *reinterpret_cast<MTState*>(mt);
+      at_round = g;
+      // the words the round can consume at most, from the stream's position on
+      PS_TRY(mt_expand_round(g, desc, desc_dev, nr, per_src, raw, st));
+    }
+    PS_TRY(launch_walk_runs_stop(indptr, indices, sources + r0, nr, (int)n_hops, alpha, use_mt ? raw : nullptr, seed,
+                                 offset, src_base + r0, np, nv, (uint32_t)n_items, runs_dev, nr_dev, hops_dev,
+                                 words_dev, err_dev, r0, st));
+    PS_TRY(launch_heap_topk(runs_dev, nr_dev, nr, (int)n_hops, (int)k, w_out ? w_out + r0 * k : nullptr,
+                            nb_out ? nb_out + r0 * k : nullptr, wn_out ? wn_out + r0 * t_norm : nullptr,
+                            nb32_out ? nb32_out + r0 * t_norm : nullptr, wn_out ? (int)t_norm : 0, st, nullptr,
+                            hops_dev));
+    if (hops_out)
+      PS_CHECK_HIP(hipMemcpyAsync(hops_out + r0, hops_dev, (size_t)nr * 4, hipMemcpyDeviceToDevice, st));
+    if (use_mt) {
+      // the chain's end decides where the next round (and the caller) goes on
+      int64_t words = 0;
+      PS_CHECK_HIP(hipMemcpyAsync(&words, words_dev, 8, hipMemcpyDeviceToHost, st));
+      PS_CHECK_HIP(hipStreamSynchronize(st));
+      MTState& g = *reinterpret_cast<MTState*>(mt);
+      g = at_round;
+      g.skip(words);
+      words_total += words;
+    }
+  }
+  if (words_out) *words_out = words_total;
+  int err = 0;
+  PS_CHECK_HIP(hipMemcpyAsync(&err, err_dev, 4, hipMemcpyDeviceToHost, st));
+  PS_CHECK_HIP(hipStreamSynchronize(st));
+  if (err != 0x7f7f7f7f) {
+    set_error("walk from source " + std::to_string(err) +
+              ": zero-degree node met (the reference's torch.randint(0) raises here) or an id >= n_items visited "
+              "(the reference's visit_counts[i, item] raises IndexError)");
+    return kErrGraph;
+  }
+  return kOk;
+}
+
 int pinsage_ppr_topk_segments(const int64_t* indptr, const int32_t* indices, int64_t n_all,
                               const int64_t* sources, int64_t n_seg, const int64_t* seg_start,
                               const uint64_t* seg_seed, const int64_t* seg_base, int64_t n_hops,

@@ -26,9 +26,24 @@ int launch_walk_runs_seg(const int64_t* indptr, const int32_t* indices, const in
 // T_norm, weights divided by the sum of those T_norm; nullable).  A source
 // without runs gives zeros with ids 0..k-1 and 0 / 0 = NaN there, as
 // visit_topk_kernel does.  n_src_dev (nullable): n_src is a capacity and the
-// count is on the device.
+// count is on the device.  hops (nullable): source s divides by hops[s]
+// instead of n_hops.
 int launch_heap_topk(const uint2* runs, const int* n_runs, int64_t n_src, int n_hops, int k, double* out_w,
                      int64_t* out_nb, float* out_wn, int32_t* out_nb32, int T_norm, hipStream_t st,
-                     const int* n_src_dev = nullptr);
+                     const int* n_src_dev = nullptr, const int* hops = nullptr);
+
+// The early-stop walks (sample_neighborhood_topt_early_stop, pinsage_model.py:
+// 55-86): a source's walk ends where the stop_np-th node reaches stop_nv visits
+// (either < 1: never).  runs / n_runs as launch_walk_runs over the hops taken,
+// hops[s] their number (launch_heap_topk's divisor).  A zero-degree node or an
+// id >= n_items among the hops taken sets err[0] to err_base + s.  Philox (raw
+// null): one wave per source.  MT19937: raw holds 3 n_hops words per source
+// from the stream's position on; one wave walks the sources in order (a stopped
+// source consumes 3 L - 1 words) and writes the words consumed to *words.
+constexpr int kStopMaxHops = 2048;
+int launch_walk_runs_stop(const int64_t* indptr, const int32_t* indices, const int64_t* sources, int64_t n_src,
+                          int n_hops, float alpha, const uint32_t* raw, uint64_t seed, uint32_t offset,
+                          int64_t src_base, int stop_np, int stop_nv, uint32_t n_items, uint2* runs, int* n_runs,
+                          int* hops, int64_t* words, int* err, int64_t err_base, hipStream_t st);
 
 }  // namespace ps

@@ -187,6 +187,281 @@ __global__ __launch_bounds__(64) void walk_runs_seg_kernel(
                         (uint64_t)(s - seg[c]), P, runs, n_runs, err, keys);
 }
 
+// ---------------------------------------------------------------- early stop
+// sample_neighborhood_topt_early_stop (pinsage_model.py:55-86): the walk of a
+// source ends at the hop where the np-th node reaches nv visits.  The stop only
+// truncates the walk, so the wave walks whole rounds of 64 hops as above and
+// cuts afterwards:
+//   * while walking, every hop's id goes through an LDS hash table of visit
+//     counts (atomicCAS claims a slot, atomicAdd counts).  The one add that
+//     takes a count from nv - 1 to nv marks an event, whatever the order of the
+//     round's lanes, so after each round the wave knows how many events lie in
+//     the hops walked; from np events on no further round is walked;
+//   * the hops walked are sorted as 64-bit (id, hop) keys.  Inside an id's run
+//     the hops ascend, so its nv-th element is the event's hop; the event hops
+//     are flagged in a table indexed by hop and the np-th set flag (ballot +
+//     popcount, in hop order) is the stop hop j*;  L = j* + 1 hops count;
+//   * the keys with hop < L are compacted (still in id order) and run-length
+//     encoded as above.  hops[s] = L is the divisor of the source's weights.
+// A zero-degree node or an id >= n_items (the reference's visit_counts[i, item]
+// raises IndexError) fails the source only if it lies at a hop < L: the
+// reference never takes the hops after its break.
+// LDS (32-bit words): trace [P] | hash keys [2P], counts [2P], overlaid after
+// the walk by the sort keys [P] x 64 bit and the flags / compacted ids [P].
+static constexpr uint32_t kHashEmpty = 0xFFFFFFFFu;
+
+template <bool kMT>
+__device__ __forceinline__ int walk_runs_stop_body(
+    const int64_t* __restrict__ indptr, const int32_t* __restrict__ indices, int64_t s, int64_t src, int n_hops,
+    float alpha, const uint32_t* __restrict__ rw, uint64_t seed, uint32_t offset, uint64_t pos, int P, int stop_np,
+    int stop_nv, uint32_t n_items, uint2* __restrict__ runs, int* __restrict__ n_runs, int* __restrict__ hops,
+    int* __restrict__ err, int64_t err_base, uint32_t* lds, bool& stopped) {
+  const int lane = threadIdx.x;
+  const unsigned long long lt = (1ull << lane) - 1;
+  uint32_t* trace = lds;
+  uint32_t* hkey = lds + P;
+  uint32_t* hcnt = lds + 3 * P;
+  uint64_t* keys = reinterpret_cast<uint64_t*>(lds + P);
+  uint32_t* aux = lds + 3 * P;
+  const int H = 2 * P;
+  const int hshift = 32 - (31 - __clz(H));
+  const bool can_stop = stop_np >= 1 && stop_nv >= 1;
+  stopped = false;
+  if (can_stop) {
+    for (int i = lane; i < H; i += 64) {
+      hkey[i] = kHashEmpty;
+      hcnt[i] = 0;
+    }
+    __syncthreads();
+  }
+  const int64_t sb = indptr[src];
+  const int64_t sd = indptr[src + 1] - sb;
+  int64_t carry_item = src;
+  bool carry_rst = true;
+  int bad_at = 0x7fffffff;  // the first hop of this lane that met a zero-degree node
+  int events = 0, W = 0;
+  for (int base = 0; base < n_hops; base += 64) {
+    const int j = base + lane;
+    const bool active = j < n_hops;
+    uint32_t r0 = 0, r1 = 0, r2 = 0;
+    if (active) {
+      if (kMT) {
+        r0 = rw[3 * j];
+        r1 = rw[3 * j + 1];
+        r2 = rw[3 * j + 2];
+      } else {
+        const uint4 r = philox10(seed, make_uint4((uint32_t)j, (uint32_t)pos, (uint32_t)(pos >> 32), offset));
+        r0 = r.x;
+        r1 = r.y;
+        r2 = r.z;
+      }
+    }
+    const bool rst = active && ((float)(r2 & 0xFFFFFFu) * 0x1p-24f < alpha);
+    const int up_rst = __shfl_up((int)rst, 1, 64);
+    const bool prev_rst = lane == 0 ? carry_rst : up_rst != 0;
+    bool known = lane == 0 || prev_rst;
+    int64_t start = (lane == 0 && !carry_rst) ? carry_item : src;
+    bool done = !active;
+    int64_t item = src;
+    for (;;) {
+      if (known && !done) {
+        int64_t b = sb, d = sd;
+        if (start != src) {
+          b = indptr[start];
+          d = indptr[start + 1] - b;
+        }
+        bool ok = false;
+        if (d > 0) {
+          const int64_t col = indices[b + (int64_t)(r0 % (uint64_t)d)];
+          const int64_t cb = indptr[col];
+          const int64_t cd = indptr[col + 1] - cb;
+          if (cd > 0) {
+            item = indices[cb + (int64_t)(r1 % (uint64_t)cd)];
+            ok = true;
+          }
+        }
+        if (!ok) bad_at = min(bad_at, j);
+        done = true;
+      }
+      if (__ballot(!done) == 0) break;
+      const int64_t prev_item = __shfl_up(item, 1, 64);
+      const bool prev_done = __shfl_up((int)done, 1, 64) != 0;
+      if (!known && lane > 0 && prev_done) {
+        known = true;
+        start = prev_item;
+      }
+    }
+    if (active) trace[j] = (uint32_t)item;
+    W = min(base + 64, n_hops);
+    if (can_stop) {
+      bool ev = false;
+      if (active) {
+        const uint32_t id = (uint32_t)item;
+        uint32_t h = (id * 2654435761u) >> hshift;
+        for (;;) {  // 2P slots for at most n_hops <= P ids: a free slot exists
+          const uint32_t old = atomicCAS(&hkey[h], kHashEmpty, id);
+          if (old == kHashEmpty || old == id) break;
+          h = (h + 1) & (uint32_t)(H - 1);
+        }
+        ev = atomicAdd(&hcnt[h], 1u) + 1u == (uint32_t)stop_nv;
+      }
+      events += __popcll(__ballot(ev));
+      if (events >= stop_np) {
+        stopped = true;
+        break;
+      }
+    }
+    const int last = min(63, n_hops - 1 - base);
+    carry_item = __shfl(item, last, 64);
+    carry_rst = __shfl((int)rst, last, 64) != 0;
+  }
+  for (int o = 32; o > 0; o >>= 1) bad_at = min(bad_at, __shfl_xor(bad_at, o, 64));
+  __syncthreads();  // the trace is written, the hash table is dead
+  int P2 = 64;
+  while (P2 < W) P2 <<= 1;
+  for (int i = lane; i < P2; i += 64) keys[i] = i < W ? ((uint64_t)trace[i] << 32) | (uint32_t)i : ~0ull;
+  __syncthreads();
+  for (int kk = 2; kk <= P2; kk <<= 1) {
+    for (int jj = kk >> 1; jj > 0; jj >>= 1) {
+      for (int i = lane; i < P2; i += 64) {
+        const int ixj = i ^ jj;
+        if (ixj > i) {
+          const uint64_t a = keys[i], b = keys[ixj];
+          const bool up = (i & kk) == 0;
+          if ((a > b) == up) {
+            keys[i] = b;
+            keys[ixj] = a;
+          }
+        }
+      }
+      __syncthreads();
+    }
+  }
+  int L = n_hops;  // not stopped: W == n_hops
+  if (stopped) {
+    for (int i = lane; i < W; i += 64) aux[i] = 0;
+    __syncthreads();
+    for (int i = lane; i < W; i += 64) {
+      const uint64_t e = keys[i];
+      const uint32_t id = (uint32_t)(e >> 32);
+      // rank stop_nv - 1 inside its id's run
+      const bool ev = i >= stop_nv - 1 && (uint32_t)(keys[i - (stop_nv - 1)] >> 32) == id &&
+                      (i < stop_nv || (uint32_t)(keys[i - stop_nv] >> 32) != id);
+      if (ev) aux[(uint32_t)e] = 1;
+    }
+    __syncthreads();
+    int seen = 0;
+    L = W;  // (events >= stop_np flags are set: the loop below finds the stop hop)
+    for (int base = 0; base < W; base += 64) {
+      const int i = base + lane;
+      const bool f = i < W && aux[i] != 0;
+      const unsigned long long m = __ballot(f);
+      const int c = __popcll(m);
+      if (seen + c >= stop_np) {
+        const bool me = f && __popcll(m & lt) == stop_np - seen - 1;
+        L = base + (__ffsll((unsigned long long)__ballot(me)) - 1) + 1;
+        break;
+      }
+      seen += c;
+    }
+    __syncthreads();  // the flags are read: aux is reused
+  }
+  // the keys of hops < L, in id order
+  int nk = 0;
+  bool oob = false;
+  for (int base = 0; base < W; base += 64) {
+    const int i = base + lane;
+    uint64_t e = 0;
+    if (i < W) e = keys[i];
+    const bool keep = i < W && (int)(uint32_t)e < L;
+    const uint32_t id = (uint32_t)(e >> 32);
+    if (keep && id >= n_items) oob = true;
+    const unsigned long long m = __ballot(keep);
+    if (keep) aux[nk + __popcll(m & lt)] = id;
+    nk += __popcll(m);
+  }
+  __syncthreads();
+  if (bad_at < L || __ballot(oob)) {
+    if (lane == 0) {
+      atomicMin(err, (int)(err_base + s < 0x7fffffff ? err_base + s : 0x7fffffff));  // the call's source index
+      n_runs[s] = 0;
+      hops[s] = n_hops;
+    }
+    stopped = false;
+    return n_hops;
+  }
+  uint32_t* run_pos = lds + P;  // [P], over the sort keys
+  int nstart = 0;
+  for (int base = 0; base < L; base += 64) {
+    const int i = base + lane;
+    const bool st = i < L && (i == 0 || aux[i] != aux[i - 1]);
+    const unsigned long long m = __ballot(st);
+    if (st) run_pos[nstart + __popcll(m & lt)] = (uint32_t)i;
+    nstart += __popcll(m);
+  }
+  __syncthreads();
+  const uint32_t self = (uint32_t)src;
+  uint2* out = runs + s * (int64_t)n_hops;
+  int nr = 0;
+  for (int base = 0; base < nstart; base += 64) {
+    const int r = base + lane;
+    uint32_t id = 0, cnt = 0;
+    if (r < nstart) {
+      const uint32_t p0 = run_pos[r];
+      id = aux[p0];
+      cnt = (r + 1 < nstart ? run_pos[r + 1] : (uint32_t)L) - p0;
+    }
+    const bool keep = r < nstart && id != self;
+    const unsigned long long m = __ballot(keep);
+    if (keep) out[nr + __popcll(m & lt)] = make_uint2(id, cnt);
+    nr += __popcll(m);
+  }
+  if (lane == 0) {
+    n_runs[s] = nr;
+    hops[s] = L;
+  }
+  return L;
+}
+
+// Philox: the draws of a source are keyed by its position, so sources are
+// independent: one wave per source.
+__global__ __launch_bounds__(64) void walk_runs_stop_kernel(
+    const int64_t* __restrict__ indptr, const int32_t* __restrict__ indices, const int64_t* __restrict__ sources,
+    int64_t n_src, int n_hops, float alpha, uint64_t seed, uint32_t offset, int64_t src_base, int P, int stop_np,
+    int stop_nv, uint32_t n_items, uint2* __restrict__ runs, int* __restrict__ n_runs, int* __restrict__ hops,
+    int* __restrict__ err, int64_t err_base) {
+  extern __shared__ __attribute__((aligned(16))) uint32_t keys[];  // [5 P]
+  const int64_t s = blockIdx.x;
+  if (s >= n_src) return;
+  bool stopped;
+  walk_runs_stop_body<false>(indptr, indices, s, sources[s], n_hops, alpha, nullptr, seed, offset,
+                             (uint64_t)(src_base + s), P, stop_np, stop_nv, n_items, runs, n_runs, hops, err,
+                             err_base, keys, stopped);
+}
+
+// MT19937: the reference breaks before the stop hop's torch.rand, so a stopped
+// source consumes 3 L - 1 words and the next source starts there: the sources
+// form a chain.  One wave walks them in order over the expanded words (3 n_hops
+// per source at most), carrying the position, and writes the words consumed.
+// (For parity with the reference, not for speed.)
+__global__ __launch_bounds__(64) void walk_runs_stop_mt_kernel(
+    const int64_t* __restrict__ indptr, const int32_t* __restrict__ indices, const int64_t* __restrict__ sources,
+    int64_t n_src, int n_hops, float alpha, const uint32_t* __restrict__ raw, int P, int stop_np, int stop_nv,
+    uint32_t n_items, uint2* __restrict__ runs, int* __restrict__ n_runs, int* __restrict__ hops,
+    int64_t* __restrict__ words, int* __restrict__ err, int64_t err_base) {
+  extern __shared__ __attribute__((aligned(16))) uint32_t keys[];  // [5 P]
+  int64_t pos = 0;
+  for (int64_t s = 0; s < n_src; ++s) {
+    bool stopped;
+    const int L = walk_runs_stop_body<true>(indptr, indices, s, sources[s], n_hops, alpha, raw + pos, 0, 0, 0, P,
+                                            stop_np, stop_nv, n_items, runs, n_runs, hops, err, err_base, keys,
+                                            stopped);
+    pos += stopped ? 3 * (int64_t)L - 1 : 3 * (int64_t)n_hops;
+    __syncthreads();  // the next source reuses the LDS
+  }
+  if (threadIdx.x == 0) *words = pos;
+}
+
 // ---------------------------------------------------------------- lane-per-source heap replay
 // libstdc++ __adjust_heap / __push_heap / __make_heap / __pop_heap /
 // __heap_select / __sort_heap over 32-bit entries ordered by count (bits 16..31).
@@ -218,10 +493,13 @@ __device__ __forceinline__ void h_adjust(uint32_t* f, int hole, int len, uint32_
   h_push(f, hole, top, v);
 }
 
+// kHops: the weights of source s are count / hops[s] (the early stop's hops
+// taken) instead of count / n_hops; the runs keep their stride n_hops.
+template <bool kHops>
 __global__ __launch_bounds__(64) void heap_topk_kernel(
     const uint2* __restrict__ runs, const int* __restrict__ n_runs, int64_t n_src, int n_hops, int k,
     int kp, int G, double* __restrict__ out_w, int64_t* __restrict__ out_nb, float* __restrict__ out_wn,
-    int32_t* __restrict__ out_nb32, int T_norm, const int* __restrict__ n_src_dev) {
+    int32_t* __restrict__ out_nb32, int T_norm, const int* __restrict__ n_src_dev, const int* __restrict__ hops) {
   extern __shared__ __attribute__((aligned(16))) uint32_t heaps[];  // [G][kp]
   __shared__ double rowsum[64];
   const int lane = threadIdx.x;
@@ -272,8 +550,9 @@ __global__ __launch_bounds__(64) void heap_topk_kernel(
       f[len] = f[0];
       h_adjust(f, 0, len, v);
     }
+    const double div = (double)(kHops ? hops[s] : n_hops);
     double sum = 0.0;
-    for (int j = 0; j < T_norm; ++j) sum += (double)(f[j] >> 16) / (double)n_hops;
+    for (int j = 0; j < T_norm; ++j) sum += (double)(f[j] >> 16) / div;
     rowsum[lane] = sum;
   }
   __syncthreads();
@@ -283,11 +562,12 @@ __global__ __launch_bounds__(64) void heap_topk_kernel(
     const int64_t sq = s0 + q;
     const uint32_t* fq = heaps + q * kp;
     const uint2* rq = runs + sq * (int64_t)n_hops;
+    const double div = (double)(kHops ? hops[sq] : n_hops);
     for (int j = lane; j < k; j += 64) {
       const uint32_t e = fq[j];
       const uint32_t ref = e & 0xFFFFu;
       const int64_t id = ref < (uint32_t)k ? (int64_t)ref : (int64_t)rq[ref - k].x;
-      const double w = (double)(e >> 16) / (double)n_hops;
+      const double w = (double)(e >> 16) / div;
       if (out_w) {
         out_w[sq * k + j] = w;
         out_nb[sq * k + j] = id;
@@ -327,9 +607,29 @@ int launch_walk_runs(const int64_t* indptr, const int32_t* indices, const int64_
   return kOk;
 }
 
+int launch_walk_runs_stop(const int64_t* indptr, const int32_t* indices, const int64_t* sources, int64_t n_src,
+                          int n_hops, float alpha, const uint32_t* raw, uint64_t seed, uint32_t offset,
+                          int64_t src_base, int stop_np, int stop_nv, uint32_t n_items, uint2* runs, int* n_runs,
+                          int* hops, int64_t* words, int* err, int64_t err_base, hipStream_t st) {
+  if (n_src <= 0) return kOk;
+  PS_REQUIRE(n_hops <= kStopMaxHops, kErrArg, "ppr_topk_early_stop: n_hops too large for the LDS tables");
+  int P = 64;
+  while (P < n_hops) P <<= 1;
+  const int lds = 5 * P * 4;  // trace | hash keys + counts (sort keys + flags)
+  if (raw)
+    hipLaunchKernelGGL(walk_runs_stop_mt_kernel, dim3(1), dim3(64), lds, st, indptr, indices, sources, n_src, n_hops,
+                       alpha, raw, P, stop_np, stop_nv, n_items, runs, n_runs, hops, words, err, err_base);
+  else
+    hipLaunchKernelGGL(walk_runs_stop_kernel, dim3((unsigned)n_src), dim3(64), lds, st, indptr, indices, sources,
+                       n_src, n_hops, alpha, seed, offset, src_base, P, stop_np, stop_nv, n_items, runs, n_runs, hops,
+                       err, err_base);
+  PS_CHECK_LAUNCH();
+  return kOk;
+}
+
 int launch_heap_topk(const uint2* runs, const int* n_runs, int64_t n_src, int n_hops, int k,
                      double* out_w, int64_t* out_nb, float* out_wn, int32_t* out_nb32, int T_norm,
-                     hipStream_t st, const int* n_src_dev) {
+                     hipStream_t st, const int* n_src_dev, const int* hops) {
   if (n_src <= 0) return kOk;
   const int kp = k | 1;
   // sources per block: 64 (one per lane) while the heaps fit 64 KB of LDS,
@@ -342,8 +642,12 @@ int launch_heap_topk(const uint2* runs, const int* n_runs, int64_t n_src, int n_
   while (G > 1 && ceil_div(n_src, G) < 1024) G >>= 1;
   const int lds = G * kp * 4;
   PS_REQUIRE(lds <= 64 * 1024, kErrArg, "ppr_topk: k too large for the LDS heaps");
-  hipLaunchKernelGGL(heap_topk_kernel, dim3((unsigned)ceil_div(n_src, G)), dim3(64), lds, st, runs,
-                     n_runs, n_src, n_hops, k, kp, G, out_w, out_nb, out_wn, out_nb32, T_norm, n_src_dev);
+  if (hops)
+    hipLaunchKernelGGL(heap_topk_kernel<true>, dim3((unsigned)ceil_div(n_src, G)), dim3(64), lds, st, runs, n_runs,
+                       n_src, n_hops, k, kp, G, out_w, out_nb, out_wn, out_nb32, T_norm, n_src_dev, hops);
+  else
+    hipLaunchKernelGGL(heap_topk_kernel<false>, dim3((unsigned)ceil_div(n_src, G)), dim3(64), lds, st, runs, n_runs,
+                       n_src, n_hops, k, kp, G, out_w, out_nb, out_wn, out_nb32, T_norm, n_src_dev, hops);
   PS_CHECK_LAUNCH();
   return kOk;
 }

@@ -10,6 +10,7 @@
 // SURVEY.md §8(b2) schema set:
 //   walk          do_random_walks (pinsage_model.py:32-53), MT19937 (torch's generator) or Philox draws
 //   ppr_topk      sample_neighborhood_topt (pinsage_model.py:88-107), fused walk + count + top-k
+//   ppr_topk_early_stop  sample_neighborhood_topt_early_stop (pinsage_model.py:55-86)
 //   frontier      relevant_nodes_per_layer_precomp's unique step (pinsage_model.py:166)
 //   linear        nn.Linear on gathered rows (+ LeakyReLU), pinsage_model.py:196-201, 209
 //   weighted_agg  (w[:, :, None] * q).sum(1) / w.sum(1), pinsage_model.py:202
@@ -165,6 +166,48 @@ std::tuple<at::Tensor, at::Tensor> ppr_topk(const at::Tensor& indptr, const at::
     run(nullptr);
   }
   return {w, nb};
+}
+
+// (w f64 [n, k], nodes i64 [n, k], hops i32 [n]) of
+// sample_neighborhood_topt_early_stop (pinsage_model.py:55-86): ppr_topk whose
+// walks end where the stop_np-th node reaches stop_nv visits; hops = the hops
+// taken (the weights' divisor), the top k over n_items columns.  Only k * 64 <=
+// n_items.  "mt19937" leaves torch's generator where the reference's break-
+// before-rand consumption leaves it (one wave walks the sources in order: for
+// parity, not speed).
+std::tuple<at::Tensor, at::Tensor, at::Tensor> ppr_topk_early_stop(
+    const at::Tensor& indptr, const at::Tensor& indices, const at::Tensor& sources, int64_t n_items, int64_t n_hops,
+    double alpha, int64_t k, int64_t stop_np, int64_t stop_nv, int64_t seed, int64_t src_base, int64_t offset,
+    const std::string& rng_mode) {
+  const bool mt = mt_mode(rng_mode);
+  check_csr(indptr, indices, sources, mt);
+  TORCH_CHECK(n_hops > 0, "n_hops must be positive");
+  c10::hip::HIPGuard guard(sources.device().index());
+  const int64_t n = sources.numel(), n_all = indptr.numel() - 1;
+  TORCH_CHECK(k >= 1 && k <= n_items, "selected index k out of range");
+  TORCH_CHECK_NOT_IMPLEMENTED(k * 64 <= n_items, "ppr_topk_early_stop: the nth_element regime (k * 64 > n_items)");
+  auto w = at::empty({n, k}, sources.options().dtype(at::kDouble));
+  auto nb = at::empty({n, k}, sources.options().dtype(at::kLong));
+  auto hops = at::empty({n}, sources.options().dtype(at::kInt));
+  if (n == 0) return {w, nb, hops};
+  const int64_t need_ws = pinsage_ppr_topk_early_stop_workspace(n, n_hops, mt ? 1 : 0);
+  auto ws = at::empty({std::min<int64_t>(need_ws, int64_t(1) << 30)}, sources.options().dtype(at::kByte));
+  auto run = [&](void* mtp) {
+    check(pinsage_ppr_topk_early_stop(indptr.data_ptr<int64_t>(), indices.data_ptr<int32_t>(), n_all, n_items,
+                                      sources.data_ptr<int64_t>(), n, n_hops, (float)alpha, k, stop_np, stop_nv, mtp,
+                                      (uint64_t)seed, (uint32_t)offset, src_base, ws.data_ptr(), ws.numel(),
+                                      w.data_ptr<double>(), nb.data_ptr<int64_t>(), nullptr, nullptr, 0,
+                                      hops.data_ptr<int32_t>(), nullptr, stream_of(sources)),
+          "ppr_topk_early_stop");
+  };
+  if (mt) {
+    TorchRng rng;
+    run(rng.mt.data());
+    rng.commit();
+  } else {
+    run(nullptr);
+  }
+  return {w, nb, hops};
 }
 
 // One step of relevant_nodes_per_layer_precomp (pinsage_model.py:162-166):
@@ -416,6 +459,9 @@ TORCH_LIBRARY(pinsage, m) {
         "str rng_mode='mt19937', int src_base=0) -> Tensor");
   m.def("ppr_topk(Tensor indptr, Tensor indices, Tensor sources, int n_hops, float alpha, int k, int seed=0, "
         "int src_base=0, int offset=0, str rng_mode='mt19937') -> (Tensor, Tensor)");
+  m.def("ppr_topk_early_stop(Tensor indptr, Tensor indices, Tensor sources, int n_items, int n_hops, float alpha, "
+        "int k, int stop_np, int stop_nv, int seed=0, int src_base=0, int offset=0, str rng_mode='mt19937') -> "
+        "(Tensor, Tensor, Tensor)");
   m.def("frontier(Tensor nodeset, Tensor nb_table, int T, int n_items=-1) -> (Tensor, Tensor)");
   m.def("linear(Tensor x, Tensor? rows, Tensor W, Tensor? b, bool lrelu) -> Tensor");
   m.def("gemm(Tensor A, bool a_kmajor, Tensor? a_idx, Tensor B, bool b_kmajor, Tensor? b_idx, int M, int N, "
@@ -432,6 +478,7 @@ TORCH_LIBRARY(pinsage, m) {
 TORCH_LIBRARY_IMPL(pinsage, CUDA, m) {
   m.impl("walk", &walk);
   m.impl("ppr_topk", &ppr_topk);
+  m.impl("ppr_topk_early_stop", &ppr_topk_early_stop);
   m.impl("frontier", &frontier);
   m.impl("linear", &linear);
   m.impl("gemm", &gemm);

@@ -154,12 +154,74 @@ def _topk_device(src, trace, n_all, n_hops, T, t_norm=0):
 _PPR_WS_CAP = 1 << 30
 
 
-def _ppr_topk_device(g, nodeset, n_hops, alpha, T, t_norm=0, philox=None, want_ref=True):
+def _ppr_topk_early_stop_device(g, n_items, nodeset, n_hops, alpha, T, early_stop, t_norm=0, philox=None,
+                                want_ref=True):
+    """_ppr_topk_device with the walks cut where the np-th node reaches nv visits
+    (early_stop = (np, nv); pinsage_model.py:55-86): the top T over n_items
+    columns of count / hops taken.  Returns (w, nb, wn, nb32, hops int32 [n]).
+    The MT19937 mode walks the sources one after another (each starts in the
+    stream where the one before stopped): it is there for parity with the
+    reference, the Philox mode for speed."""
+    g = _as_csr(g)
+    T, n_items = int(T), int(n_items)
+    stop_np, stop_nv = (int(v) for v in early_stop)
+    if T * 64 > n_items:
+        raise NotImplementedError(f"early stop: T * 64 > n_items ({T} * 64 > {n_items}) is torch's nth_element "
+                                  "regime of topk, which the early-stop sampler does not restate")
+    dev = nat.device()
+    indptr, indices = g.device_csr(dev)
+    src = torch.as_tensor(nodeset).reshape(-1).to(device=dev, dtype=torch.int64).contiguous()
+    n = int(src.shape[0])
+    w = torch.empty((n, T), dtype=torch.float64, device=dev) if want_ref else None
+    nb = torch.empty((n, T), dtype=torch.int64, device=dev) if want_ref else None
+    wn = nb32 = None
+    if t_norm:
+        wn = torch.empty((n, t_norm), dtype=torch.float32, device=dev)
+        nb32 = torch.empty((n, t_norm), dtype=torch.int32, device=dev)
+    hops = torch.empty(n, dtype=torch.int32, device=dev)
+    if n == 0:
+        return w, nb, wn, nb32, hops
+    L = nat.lib()
+    mt_mode = _RNG_MODE == "mt19937" and philox is None
+    if mt_mode and g.max_degree() >= (1 << 28):
+        raise RuntimeError("degree >= 2^28: torch.randint switches to 64-bit draws; use rng mode 'philox'")
+    need = L.pinsage_ppr_topk_early_stop_workspace(n, int(n_hops), 1 if mt_mode else 0)
+    ws = torch.empty(min(need, _PPR_WS_CAP), dtype=torch.uint8, device=dev)
+
+    def run(mt_p, seed, base):
+        nat.check(L.pinsage_ppr_topk_early_stop(
+            nat.ptr(indptr), nat.ptr(indices), g.number_of_nodes(), n_items, nat.ptr(src), n, int(n_hops),
+            float(np.float32(alpha)), T, stop_np, stop_nv, mt_p, seed, 0, base, nat.ptr(ws), ws.numel(), nat.ptr(w),
+            nat.ptr(nb), nat.ptr(wn), nat.ptr(nb32), int(t_norm), nat.ptr(hops), None, nat.stream_ptr()),
+            "ppr_topk_early_stop")
+
+    if mt_mode:
+        with nat.torch_rng() as mt:  # left where the last source stopped
+            run(mt.p, 0, 0)
+    else:
+        if philox is None:
+            with nat.torch_rng() as mt:
+                d = mt.draws(2)
+            seed, base = (int(d[0]) << 32) | int(d[1]), 0
+        else:
+            seed, base = philox
+        run(None, seed, int(base))
+    return w, nb, wn, nb32, hops
+
+
+def _ppr_topk_device(g, nodeset, n_hops, alpha, T, t_norm=0, philox=None, want_ref=True, early_stop=None,
+                     n_items=None):
     """Top-T of visit_prob for each source (pinsage_model.py:32-53, 88-107) with
     the fused kernel; same draws as _walk_device (+ _topk_device).  Returns
     (w f64, nb i64, wn f32, nb32 i32) on the device (None where not asked).
     Tiny graphs (T * 64 > N_all: torch's nth_element regime) take the walk +
-    visit_topk kernels."""
+    visit_topk kernels.  early_stop = (np, nv): the early-stop sampler over
+    n_items columns (_ppr_topk_early_stop_device)."""
+    if early_stop is not None:
+        if n_items is None:
+            raise ValueError("early_stop needs n_items (the top-k row width)")
+        return _ppr_topk_early_stop_device(g, n_items, nodeset, n_hops, alpha, T, early_stop, t_norm=t_norm,
+                                           philox=philox, want_ref=want_ref)[:4]
     g = _as_csr(g)
     n_all = g.number_of_nodes()
     T = int(T)
@@ -209,6 +271,20 @@ def _ppr_topk_device(g, nodeset, n_hops, alpha, T, t_norm=0, philox=None, want_r
 def sample_neighborhood_topt(g, n_items, nodeset, n_hops, alpha, T):
     """visit_prob.topk(T, 1) as a ``torch.return_types.topk`` (pinsage_model.py:103-107)."""
     w, nb, _, _ = _ppr_topk_device(g, nodeset, n_hops, alpha, int(T))
+    out_dev = torch.as_tensor(nodeset).device
+    return torch.return_types.topk((w.to(out_dev), nb.to(out_dev)))
+
+
+def sample_neighborhood_topt_early_stop(g, n_items, nodeset, n_hops, alpha, T, np, nv):
+    """sample_neighborhood_topt with the PinSage paper's early termination
+    (pinsage_model.py:55-86, unused there for its speed): a source's walk ends
+    as soon as ``np`` nodes have been visited ``nv`` times.  The weights are the
+    visit counts over the hops taken divided by their number, the top T is
+    taken over ``n_items`` columns.  In the default mt19937 mode values, indices
+    and the generator's state afterwards are the reference's (that mode walks
+    the sources one after another: use 'philox' for speed).  T * 64 > n_items
+    (torch's nth_element regime) raises NotImplementedError."""
+    w, nb, _, _, _ = _ppr_topk_early_stop_device(g, n_items, nodeset, n_hops, alpha, int(T), (np, nv))
     out_dev = torch.as_tensor(nodeset).device
     return torch.return_types.topk((w.to(out_dev), nb.to(out_dev)))
 
@@ -315,7 +391,7 @@ def precompute_neighborhoods_topt(g, n_items, n_hops, alpha, T, path):
     return (all_w, all_nb)
 
 
-def precompute_device_table(g, n_items, n_hops, alpha, T, T_precomp=DEF_T_PRECOMP, chunk=1 << 18):
+def precompute_device_table(g, n_items, n_hops, alpha, T, T_precomp=DEF_T_PRECOMP, chunk=1 << 18, early_stop=None):
     """The model's neighbourhood table built and kept on the device: for every
     item, the first T of its top-T_precomp PPR neighbours (the rows
     precompute_neighborhoods_topt returns, cut to [:, :T] as the model reads
@@ -323,11 +399,17 @@ def precompute_device_table(g, n_items, n_hops, alpha, T, T_precomp=DEF_T_PRECOM
     (pinsage_model.py:202).  Same draws and positions as
     precompute_neighborhoods_topt (one process), but the [n, T_precomp] f64 + i64
     table never exists: at 80M items it would be 128 GB of host memory.  Returns
-    a device table PinSageModel / PinSage accept as ``nbhds``."""
+    a device table PinSageModel / PinSage accept as ``nbhds``.  early_stop =
+    (np, nv): the walks stop early (sample_neighborhood_topt_early_stop), in
+    Philox mode only: the chunks are positioned absolutely in the stream, which
+    MT19937 words consumed by a data-dependent number of hops cannot be."""
     dev = nat.device()
     T, T_precomp = int(T), int(T_precomp)
     if T > T_precomp:
         raise ValueError("T > T_precomp")
+    if early_stop is not None and _RNG_MODE == "mt19937":
+        raise ValueError("precompute_device_table: early_stop needs rng mode 'philox' (a stopped walk's MT19937 "
+                         "consumption depends on its hops, so chunks have no absolute stream position)")
     nb32 = torch.empty((n_items, T), dtype=torch.int32, device=dev)
     wn = torch.empty((n_items, T), dtype=torch.float32, device=dev)
     st0 = torch.get_rng_state().numpy().copy()
@@ -342,7 +424,8 @@ def precompute_device_table(g, n_items, n_hops, alpha, T, T_precomp=DEF_T_PRECOM
             _set_stream_position(st0, 3 * int(n_hops) * i)
         ids = torch.arange(i, min(i + chunk, n_items), dtype=torch.int64, device=dev)
         _, _, w_c, nb_c = _ppr_topk_device(g, ids, n_hops, alpha, T_precomp, t_norm=T,
-                                           philox=None if mt_mode else (philox, i), want_ref=False)
+                                           philox=None if mt_mode else (philox, i), want_ref=False,
+                                           early_stop=early_stop, n_items=n_items)
         nb32[i:i + ids.shape[0]] = nb_c
         wn[i:i + ids.shape[0]] = w_c
     if mt_mode:
@@ -373,14 +456,17 @@ def _frontier_step(nodeset_dev, nb32, T, n_items):
     return out[:int(cnt.item())].to(torch.int64)
 
 
-def relevant_nodes_per_layer(g, n_items, nodeset, n_layers, n_hops, alpha, T):
-    """Computation graph with on-the-fly sampling (pinsage_model.py:142-154)."""
+def relevant_nodes_per_layer(g, n_items, nodeset, n_layers, n_hops, alpha, T, early_stop=None):
+    """Computation graph with on-the-fly sampling (pinsage_model.py:142-154).
+    early_stop = (np, nv): every layer samples with
+    sample_neighborhood_topt_early_stop (the reference's commented call, :149-150)."""
     out_dev = torch.as_tensor(nodeset).device
     dev = nat.device()
     S = []
     cur = torch.as_tensor(nodeset).to(dev, torch.int64)
     for _ in reversed(range(0, n_layers)):
-        w, nb, _, nb32 = _ppr_topk_device(g, cur, n_hops, alpha, int(T), t_norm=int(T))
+        w, nb, _, nb32 = _ppr_topk_device(g, cur, n_hops, alpha, int(T), t_norm=int(T), early_stop=early_stop,
+                                          n_items=n_items)
         S.insert(0, (cur.to(out_dev), w.to(out_dev), nb.to(out_dev)))
         # unique(cat(nb.flatten(), cur)): rows of nb belong to cur's positions
         table = torch.zeros((g.number_of_nodes(), int(T)), dtype=torch.int32, device=dev)

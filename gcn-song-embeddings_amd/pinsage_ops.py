@@ -1,7 +1,7 @@
 """torch.ops.pinsage: the hot path's kernels as PyTorch-ROCm operators.
 
 ``libpinsage_torch.so`` (csrc/torch_ops.cpp, built in-tree by csrc/Makefile)
-registers the schemas of SURVEY.md §8(b2) -- walk, ppr_topk, frontier,
+registers the schemas of SURVEY.md §8(b2) -- walk, ppr_topk, ppr_topk_early_stop, frontier,
 gather_rows / scatter_add_rows, linear, concat_linear_lrelu_l2norm (+
 norm_lrelu_backward), gemm, weighted_agg (+ weighted_agg_backward),
 segment_wmean -- on the HIP device, each calling libpinsage_hip.so's C-ABI on

@@ -136,6 +136,32 @@ int pinsage_ppr_topk(const int64_t* indptr, const int32_t* indices, int64_t n_al
                      void* mt, uint64_t seed, uint32_t offset, int64_t src_base, void* ws,
                      int64_t ws_bytes, double* w_out, int64_t* nb_out, float* wn_out,
                      int32_t* nb32_out, int64_t t_norm, void* stream);
+/* sample_neighborhood_topt_early_stop (pinsage_model.py:55-86): pinsage_ppr_topk
+ * whose walk from a source ends at the hop where the stop_np-th node reaches
+ * stop_nv visits (visits to the source itself count; stop_np < 1 or stop_nv < 1
+ * never stops).  With L the hops taken, the weights are count / L over the
+ * first L hops, and the top k is taken over n_items columns (the reference's
+ * visit_counts is [n, n_items]): only the partial_sort regime, k * 64 <=
+ * n_items, else PINSAGE_ERR_ARG.  n_hops <= 2048.  A zero-degree node or an id
+ * >= n_items among the hops taken gives PINSAGE_ERR_GRAPH (the message names
+ * the first such source).  hops_out (nullable) int32 [n_src] device: L per
+ * source.  Philox mode draws as pinsage_ppr_topk (a stop only truncates), one
+ * wave per source.  MT19937 mode (mt != null) is for parity with the reference,
+ * not for speed: a stopped source consumes 3 L - 1 words (the break comes
+ * before that hop's torch.rand), an unstopped one 3 n_hops, so each source
+ * starts where the one before stopped and one wave walks them in order; the
+ * host state is left advanced by the words consumed, also written to
+ * *words_out (nullable, host; 0 in Philox mode).  ws: device bytes >=
+ * pinsage_ppr_topk_early_stop_workspace(n_src, n_hops, mt != null) (smaller
+ * workspaces run in rounds, each starting where the last one ended).
+ * Synchronises the stream. */
+int64_t pinsage_ppr_topk_early_stop_workspace(int64_t n_src, int64_t n_hops, int rng_mt);
+int pinsage_ppr_topk_early_stop(const int64_t* indptr, const int32_t* indices, int64_t n_all, int64_t n_items,
+                                const int64_t* sources, int64_t n_src, int64_t n_hops, float alpha, int64_t k,
+                                int64_t stop_np, int64_t stop_nv, void* mt, uint64_t seed, uint32_t offset,
+                                int64_t src_base, void* ws, int64_t ws_bytes, double* w_out, int64_t* nb_out,
+                                float* wn_out, int32_t* nb32_out, int64_t t_norm, int32_t* hops_out,
+                                int64_t* words_out, void* stream);
 /* pinsage_ppr_topk (Philox mode) over n_seg consecutive segments of sources in
  * one call: segment i = sources[seg_start[i] .. seg_start[i+1]) is keyed by
  * (seg_seed[i], hop, seg_base[i] + j, offset), so each segment draws exactly
