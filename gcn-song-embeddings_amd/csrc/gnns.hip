@@ -15,7 +15,8 @@
 namespace ps {
 
 // out[i, :] = sum_j w_j * h[cols_j, :] / den_i,  den_i = max(sum_j |w_j|, 1e-12)
-// (normalize) or 1.  Rows whose neighbours are out of [0, n_h) skip them.
+// (normalize) or 1.  Rows whose neighbours are out of [0, n_h) skip them, in
+// the sum and in den_i.
 template <bool VEC>
 __global__ __launch_bounds__(256) void segment_wmean_kernel(
     const float* __restrict__ h, int64_t ldh, int64_t n_h, int d, const int64_t* __restrict__ seg_ptr,
@@ -28,7 +29,8 @@ __global__ __launch_bounds__(256) void segment_wmean_kernel(
   float inv = 1.f;
   if (normalize) {
     float s = 0.f;
-    for (int64_t j = b + lane; j < e; j += 64) s += fabsf(w[j]);
+    for (int64_t j = b + lane; j < e; j += 64)
+      if ((uint64_t)(int64_t)cols[j] < (uint64_t)n_h) s += fabsf(w[j]);  // (a skipped neighbour has no weight)
     s = wave_sum(s);
     inv = 1.f / fmaxf(s, 1e-12f);
   }

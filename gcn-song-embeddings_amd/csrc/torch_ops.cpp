@@ -243,11 +243,15 @@ std::tuple<at::Tensor, at::Tensor> frontier(const at::Tensor& nodeset, const at:
   return {out.narrow(0, 0, cnt.item<int32_t>()).to(at::kLong), local_idx};
 }
 
-// y = x[rows] W^T (+ b) (LeakyReLU 0.01 if lrelu); rows int32 or none
+// y = x[rows] W^T (+ b) (LeakyReLU 0.01 if lrelu); rows int32 or none.  The
+// values of rows are not checked against x's rows: that would cost a device
+// sync the op does not otherwise pay (conv_layer validates its ids once).
 at::Tensor linear(const at::Tensor& x, const c10::optional<at::Tensor>& rows, const at::Tensor& W,
                   const c10::optional<at::Tensor>& b, bool lrelu) {
-  TORCH_CHECK(x.is_cuda() && x.scalar_type() == at::kFloat && x.stride(1) == 1, "x: f32 device rows");
+  TORCH_CHECK(x.is_cuda() && x.scalar_type() == at::kFloat && x.dim() == 2 && x.stride(1) == 1,
+              "x: f32 device rows [n, >= in_features]");
   need(W, at::kFloat, "W");
+  TORCH_CHECK(W.dim() == 2, "W: [out_features, in_features]");
   c10::hip::HIPGuard guard(x.device().index());
   const int64_t K = W.size(1), N = W.size(0);
   TORCH_CHECK(x.size(1) >= K, "x narrower than W's in_features");
@@ -261,6 +265,7 @@ at::Tensor linear(const at::Tensor& x, const c10::optional<at::Tensor>& rows, co
   const float* bias = nullptr;
   if (b.has_value()) {
     need(*b, at::kFloat, "b");
+    TORCH_CHECK(b->numel() == N, "b: [out_features], got ", b->numel(), " elements for ", N, " features");
     bias = b->data_ptr<float>();
   }
   auto y = at::empty({M, N}, x.options());
@@ -271,12 +276,29 @@ at::Tensor linear(const at::Tensor& x, const c10::optional<at::Tensor>& rows, co
   return y;
 }
 
-// C [M][N] = op(A) op(B): a_kmajor: A [M][K] (rows gathered by a_idx) else [K][M];
-// b_kmajor: B [N][K] else [K][N] (k-rows gathered by b_idx)
+// C [M][N] = op(A) op(B): a_kmajor: A [M][K] (rows gathered by a_idx) else [K][M]
+// (k-rows gathered by a_idx); b_kmajor: B [N][K] (no gather) else [K][N] (k-rows
+// gathered by b_idx).  M, N, K are checked against the operands' shapes and the
+// index tensors' lengths; the index values are not (a device sync the op does
+// not otherwise pay): an index outside its operand's rows is the caller's error.
 at::Tensor gemm(const at::Tensor& A, bool a_kmajor, const c10::optional<at::Tensor>& a_idx, const at::Tensor& B,
                 bool b_kmajor, const c10::optional<at::Tensor>& b_idx, int64_t M, int64_t N, int64_t K) {
+  TORCH_CHECK(A.dim() == 2 && B.dim() == 2, "A and B must be 2-D");
   TORCH_CHECK(A.is_cuda() && A.scalar_type() == at::kFloat && A.stride(1) == 1, "A: f32 device rows");
   TORCH_CHECK(B.is_cuda() && B.scalar_type() == at::kFloat && B.stride(1) == 1, "B: f32 device rows");
+  TORCH_CHECK(M >= 0 && N >= 1 && K >= 0, "gemm: M, K >= 0 and N >= 1");
+  // A's rows are its gathered extent (M if K-major, K if M-major), B's likewise (N or K)
+  const int64_t a_rows = a_kmajor ? M : K, a_cols = a_kmajor ? K : M;
+  const int64_t b_rows = b_kmajor ? N : K, b_cols = b_kmajor ? K : N;
+  TORCH_CHECK(A.size(1) >= a_cols, "gemm: A has ", A.size(1), " columns, the layout needs ", a_cols);
+  TORCH_CHECK(B.size(1) >= b_cols, "gemm: B has ", B.size(1), " columns, the layout needs ", b_cols);
+  TORCH_CHECK(!(b_kmajor && b_idx.has_value()), "gemm: b_idx gathers the k-rows of an N-major B only");
+  const int64_t a_have = a_idx.has_value() ? a_idx->numel() : A.size(0);
+  const int64_t b_have = b_idx.has_value() ? b_idx->numel() : B.size(0);
+  TORCH_CHECK(a_idx.has_value() ? a_have == a_rows : a_have >= a_rows, "gemm: ", a_idx.has_value() ? "a_idx" : "A",
+              " has ", a_have, " rows, the layout needs ", a_rows);
+  TORCH_CHECK(b_idx.has_value() ? b_have == b_rows : b_have >= b_rows, "gemm: ", b_idx.has_value() ? "b_idx" : "B",
+              " has ", b_have, " rows, the layout needs ", b_rows);
   c10::hip::HIPGuard guard(A.device().index());
   const int32_t* ai = nullptr;
   const int32_t* bi = nullptr;
@@ -298,11 +320,13 @@ at::Tensor gemm(const at::Tensor& A, bool a_kmajor, const c10::optional<at::Tens
   return C;
 }
 
-// agg[f] = sum_t w[f][t] q[loc[f][t]]  (w already normalised)
+// agg[f] = sum_t w[f][t] q[loc[f][t]]  (w already normalised).  loc's values are
+// not checked against q's rows (a device sync the op does not otherwise pay).
 at::Tensor weighted_agg(const at::Tensor& q, const at::Tensor& loc, const at::Tensor& w) {
   need(q, at::kFloat, "q");
   need(loc, at::kInt, "loc");
   need(w, at::kFloat, "w");
+  TORCH_CHECK(q.dim() == 2, "q: [n_q, hid]");
   TORCH_CHECK(loc.sizes() == w.sizes() && loc.dim() == 2, "loc and w: [n, T]");
   c10::hip::HIPGuard guard(q.device().index());
   const int64_t n = loc.size(0), T = loc.size(1), hid = q.size(1);
@@ -314,13 +338,19 @@ at::Tensor weighted_agg(const at::Tensor& q, const at::Tensor& loc, const at::Te
   return agg;
 }
 
-// out[i] = sum_{j in [seg[i], seg[i+1])} w[j] h[cols[j]]  (/ sum |w| if normalize)
+// out[i] = sum_{j in [seg[i], seg[i+1])} w[j] h[cols[j]]  (/ sum |w| if normalize);
+// a column outside [0, h rows) is skipped, in the sum and in the normalisation.
+// seg's values are not checked against cols' length (ascending, seg[-1] <=
+// cols.numel() is the caller's: a device sync the op does not otherwise pay).
 at::Tensor segment_wmean(const at::Tensor& h, const at::Tensor& seg, const at::Tensor& cols, const at::Tensor& w,
                          bool normalize) {
-  TORCH_CHECK(h.is_cuda() && h.scalar_type() == at::kFloat && h.stride(1) == 1, "h: f32 device rows");
+  TORCH_CHECK(h.is_cuda() && h.scalar_type() == at::kFloat && h.dim() == 2 && h.stride(1) == 1,
+              "h: f32 device rows");
   need(seg, at::kLong, "seg");
   need(cols, at::kInt, "cols");
   need(w, at::kFloat, "w");
+  TORCH_CHECK(cols.numel() == w.numel(), "cols and w lengths differ: ", cols.numel(), " and ", w.numel());
+  TORCH_CHECK(seg.numel() >= 1, "seg: [n_seg + 1], at least one element");
   c10::hip::HIPGuard guard(h.device().index());
   const int64_t n_seg = seg.numel() - 1, d = h.size(1);
   auto out = at::empty({n_seg, d}, h.options());
@@ -337,6 +367,10 @@ at::Tensor weighted_agg_backward(const at::Tensor& dagg, const at::Tensor& loc, 
                                  int64_t n_q) {
   need(loc, at::kInt, "loc");
   need(w, at::kFloat, "w");
+  TORCH_CHECK(loc.sizes() == w.sizes() && loc.dim() == 2, "loc and w: [n, T]");
+  TORCH_CHECK(dagg.is_cuda() && dagg.scalar_type() == at::kFloat && dagg.dim() == 2 && dagg.size(0) == loc.size(0),
+              "dagg: f32 device [n, hid] with loc's rows");
+  TORCH_CHECK(n_q >= 0, "n_q must not be negative");
   const int64_t T = loc.size(1);
   auto flat = loc.reshape({-1}).to(at::kLong);
   auto order = std::get<1>(at::sort(flat, /*stable=*/true, 0, false));

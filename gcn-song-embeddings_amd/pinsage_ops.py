@@ -44,6 +44,13 @@ def _pad4(t, fill=0):
     return t if r == 0 else torch.cat([t, t.new_full((r,) + tuple(t.shape[1:]), fill)])
 
 
+def _pad4_cols(t):
+    """t [n, c] with zero columns up to a multiple of 4 (pinsage::gemm takes an
+    M-major A's M and every K in fours; a zero feature column adds nothing)"""
+    r = (-t.shape[1]) % 4
+    return t if r == 0 else torch.cat([t, t.new_zeros((t.shape[0], r))], 1)
+
+
 def _linear_setup(ctx, inputs, output):
     x, rows, W, b, lrelu = inputs
     ctx.save_for_backward(x, rows, W, output)
@@ -61,14 +68,17 @@ def _linear_backward(ctx, dy):
     n = dz.shape[0]
     ops = torch.ops.pinsage
     dW = db = dx = None
+    # out_features in fours for the GEMMs: zero columns of dz, zero rows of W
+    dzp = _pad4_cols(dz)
+    Np = dzp.shape[1]
     if ctx.needs_input_grad[2]:
         idx = rows if rows is not None else torch.arange(n, dtype=torch.int32, device=dz.device)
-        dz4, idx4 = _pad4(dz), _pad4(idx)
-        dW = ops.gemm(dz4, False, None, x, False, idx4, N, K, dz4.shape[0])
+        dz4, idx4 = _pad4(dzp), _pad4(idx)
+        dW = ops.gemm(dz4, False, None, x, False, idx4, Np, K, dz4.shape[0])[:N]
     if ctx.has_b and ctx.needs_input_grad[3]:
         db = dz.sum(0)
     if ctx.needs_input_grad[0]:
-        d_rows = ops.gemm(dz, True, None, W, False, None, n, K, N)
+        d_rows = ops.gemm(dzp, True, None, _pad4(W), False, None, n, K, Np)
         dx = torch.zeros_like(x)
         if rows is None:
             dx[:n, :K] += d_rows
@@ -131,23 +141,28 @@ def _cat_backward(ctx, dy, _dnorms):
     n = y.shape[0]
     dp = ops.norm_lrelu_backward(dy.contiguous(), y, norms)
     dh = dagg = dW = db = None
+    # out_features in fours for the GEMMs: zero columns of dp, zero rows of W
+    dpp = _pad4_cols(dp)
+    outp = dpp.shape[1]
+    Wp = _pad4(W)
     if ctx.needs_input_grad[3]:
-        dp4 = _pad4(dp)
+        dp4 = _pad4(dpp)
         idx = rows.to(torch.int32) if rows is not None else torch.arange(n, dtype=torch.int32, device=dp.device)
         idx4 = _pad4(idx)
-        dW = torch.cat([ops.gemm(dp4, False, None, h, False, idx4, out, d, dp4.shape[0]),
-                        ops.gemm(dp4, False, None, _pad4(agg.contiguous()), False, None, out, hid, dp4.shape[0])], 1)
+        dW = torch.cat([ops.gemm(dp4, False, None, h, False, idx4, outp, d, dp4.shape[0]),
+                        ops.gemm(dp4, False, None, _pad4(agg.contiguous()), False, None, outp, hid,
+                                 dp4.shape[0])], 1)[:out]
     if ctx.needs_input_grad[4]:
         db = dp.sum(0)
     if ctx.needs_input_grad[0]:
-        d_rows = ops.gemm(dp, True, None, W[:, :d], False, None, n, d, out)
+        d_rows = ops.gemm(dpp, True, None, Wp[:, :d], False, None, n, d, outp)
         if rows is None:
             dh = torch.zeros_like(h)
             dh[:n, :d] += d_rows
         else:
             dh = ops.scatter_add_rows(d_rows, rows, h.shape[0], h.shape[1])
     if ctx.needs_input_grad[2]:
-        dagg = ops.gemm(dp, True, None, W[:, d:], False, None, n, hid, out)
+        dagg = ops.gemm(dpp, True, None, Wp[:, d:], False, None, n, hid, outp)
     return dh, None, dagg, dW, db
 
 
