@@ -173,6 +173,13 @@ _SIGS = {
     "pinsage_stepper_step": (ctypes.c_int, [vp, vp, i64, vp, vp, vp, vp]),
     "pinsage_segment_wmean": (ctypes.c_int, [vp, i64, i64, i64, vp, vp, vp, i64, ctypes.c_int, vp, i64,
                                              vp]),
+    "pinsage_gat_partial_rows": (i64, [i64]),
+    "pinsage_gat_node_scores": (ctypes.c_int, [vp, i64, i64, i64, vp, vp, i64, vp, vp, vp]),
+    "pinsage_gat_forward": (ctypes.c_int, [vp, i64, i64, i64, vp, vp, vp, vp, i64, i64, vp, vp, vp, i64, vp, vp]),
+    "pinsage_gat_backward_edges": (ctypes.c_int, [vp, i64, i64, i64, vp, vp, vp, vp, i64, i64, vp, vp, vp, vp, i64,
+                                                  vp, vp, vp]),
+    "pinsage_gat_backward_rows": (ctypes.c_int, [vp, i64, i64, i64, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, i64,
+                                                 i64, vp, i64, vp, i64, vp, vp, vp, vp]),
     "pinsage_knn_scratch_bytes": (i64, [i64, i64]),
     "pinsage_knn_cosine": (ctypes.c_int, [vp, i64, i64, i64, vp, i64, i64, f32, vp, i64, vp, vp, vp]),
     "pinsage_rank_scratch_bytes": (i64, [i64, i64]),

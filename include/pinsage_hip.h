@@ -693,6 +693,59 @@ int pinsage_segment_wmean(const float* h, int64_t ldh, int64_t n_h, int64_t d, c
                           const int32_t* cols, const float* w, int64_t n_seg, int normalize, float* out,
                           int64_t ldo, void* stream);
 
+/* ------------------------------------------------------------------ lib/gnns GAT aggregator
+ * GNN_model.aggregate with gat=True (lib/gnns/GNNs_unsupervised.py:449-465,
+ * 555-567): a softmax over each node's whole neighbourhood of
+ * leaky_relu(att([h_own || h_nb]), 0.2) * sqrt(edge count), then mask.mm(h);
+ * here an edge softmax fused with the row gather, no [F, U] mask and no
+ * gathered [nnz, d] buffers.  Segment i has entries j in [seg_ptr[i],
+ * seg_ptr[i+1]) with hrow[j] (int32 row of h) and c[j] >= 0; own[i] is the h
+ * row of the segment's node; a = [a_l | a_r] f32 [2 d] (att.weight[0]):
+ *   e_ij = s_l[own_i] + s_r[hrow_j],  s_l[u] = a_l . h[u],  s_r[u] = a_r . h[u]
+ *   m_ij = (e_ij > 0 ? e_ij : 0.2 e_ij) * c_ij
+ *   kept: m_ij != 0, hrow_j and own_i in [0, n_h)
+ *   p_ij = exp(m_ij - M_i) / sum_kept exp(m_ik - M_i),  M_i = max_kept m_ik
+ *   out_i = sum_j p_ij h[hrow_j]          (nothing kept: p = 0, a zero row)
+ * and for dout f32 [n_seg][lddo]:
+ *   g_ij = dout_i . h[hrow_j],  gbar_i = sum_j p_ij g_ij
+ *   de_ij = p_ij (g_ij - gbar_i) c_ij (e_ij > 0 ? 1 : 0.2),  s_i = sum_j de_ij
+ *   dh[hrow_j] += p_ij dout_i + de_ij a_r,  dh[own_i] += s_i a_l
+ *   da = [sum_i s_i h[own_i] | sum_ij de_ij h[hrow_j]]
+ * All pointers are device pointers; seg_ptr, segT, own_ptr int64, the other
+ * index arrays int32; 0 < d <= 2^20, n_h <= INT32_MAX, leading dimensions >=
+ * d.  Rows are read 16 bytes at a time when d, the leading dimensions and the
+ * base pointers allow it, else 4.  No atomics and fixed summation orders: two
+ * identical calls give the same bits.  A refused call (PINSAGE_ERR_ARG)
+ * launches nothing.
+ *
+ * node_scores: s_l[u], s_r[u] for u = rows[t], t < n_rows (rows null: u = t,
+ *   n_rows <= n_h); other elements of s_l, s_r [n_h] are left alone.
+ * forward: out [n_seg][ldo] and p [nnz] (every entry written, 0 where dropped).
+ * backward_edges: de [nnz], s [n_seg] from the forward's p.
+ * backward_rows: rows_u int32 [n_rows] ascending and unique, covering every
+ *   in-range hrow and own; segT [n_rows + 1] over (entT, segofT) = the entries
+ *   k with hrow[k] == rows_u[t] and their segments; own_ptr [n_rows + 1] over
+ *   own_seg = the segments i with own[i] == rows_u[t].  Writes row rows_u[t]
+ *   of dh [n_h][lddh] (the other rows are the caller's: zero them), coef
+ *   [2 n_rows] and partial [pinsage_gat_partial_rows(n_rows)][2 d] (scratch)
+ *   and da [2 d]. */
+int64_t pinsage_gat_partial_rows(int64_t n_rows);
+int pinsage_gat_node_scores(const float* h, int64_t ldh, int64_t n_h, int64_t d, const float* a, const int32_t* rows,
+                            int64_t n_rows, float* s_l, float* s_r, void* stream);
+int pinsage_gat_forward(const float* h, int64_t ldh, int64_t n_h, int64_t d, const int64_t* seg_ptr,
+                        const int32_t* hrow, const float* c, const int32_t* own, int64_t n_seg, int64_t nnz,
+                        const float* s_l, const float* s_r, float* out, int64_t ldo, float* p, void* stream);
+int pinsage_gat_backward_edges(const float* h, int64_t ldh, int64_t n_h, int64_t d, const int64_t* seg_ptr,
+                               const int32_t* hrow, const float* c, const int32_t* own, int64_t n_seg, int64_t nnz,
+                               const float* s_l, const float* s_r, const float* p, const float* dout, int64_t lddo,
+                               float* de, float* s, void* stream);
+int pinsage_gat_backward_rows(const float* h, int64_t ldh, int64_t n_h, int64_t d, const float* a,
+                              const int32_t* rows_u, int64_t n_rows, const int64_t* segT, const int32_t* entT,
+                              const int32_t* segofT, const int64_t* own_ptr, const int32_t* own_seg, const float* p,
+                              const float* de, const float* s, int64_t nnz, int64_t n_seg, const float* dout,
+                              int64_t lddo, float* dh, int64_t lddh, float* coef, float* partial, float* da,
+                              void* stream);
+
 /* ------------------------------------------------------------------ cosine kNN
  * knn_from_emb (baselines.py:91-103) over cosine_sim_ab (baselines.py:69-77), the
  * evaluation consumer of the embeddings (eval.py:112-143 save_knn, k = 1000):
